@@ -89,7 +89,16 @@ std::vector<size_t> Mailbox::wait(int64_t tag, size_t k, double timeout_s) {
   if (timeout_s < 0) {
     cv_.wait(lk, [&] { return count() >= k; });
   } else {
+#if defined(__SANITIZE_THREAD__)
+    // wait_for sleeps in pthread_cond_clockwait, which GCC 11's ThreadSanitizer runtime does not intercept:
+    // it misses the unlock inside the wait and reports a writer's lock as a "double lock" whenever the
+    // waiter really blocks. A system_clock deadline goes through pthread_cond_timedwait, which it knows.
+    const auto span = std::chrono::duration_cast<std::chrono::system_clock::duration>(
+        std::chrono::duration<double>(timeout_s));
+    cv_.wait_until(lk, std::chrono::system_clock::now() + span, [&] { return count() >= k; });
+#else
     cv_.wait_for(lk, std::chrono::duration<double>(timeout_s), [&] { return count() >= k; });
+#endif
   }
   std::vector<size_t> ids;
   for (size_t i = 0; i < nslots_; ++i)

@@ -11,7 +11,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0 PYTHONPATH=$(pwd) OMP_NUM_THREADS=2 GARFIELD
 for atk in none reverse; do
   A=""; [ "$atk" = none ] || A="--ps-attack $atk"
   timeout -k 10 600 python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 2966${#atk} \
-    bench.py --gpus 8 --steps 3 --warmup 1 --no-fp32 --gar trimmed-mean --f 1 --num-ps 3 --fps 1 --mar median \
+    bench.py --gpus 8 --steps 3 --warmup 1 --full --no-fp32 --gar trimmed-mean --f 1 --num-ps 3 --fps 1 --mar median \
     --workers-per-gpu 1 --no-graph $A > $O/cfg5_$atk.json.log 2>&1 || { echo "cfg5 $atk failed"; tail -20 $O/cfg5_$atk.json.log; exit 1; }
   grep '^{' $O/cfg5_$atk.json.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$atk', d['ms_per_step'], d['config']['parallelism'], d.get('replicas_identical'), d.get('replica_checksums'))"
 done

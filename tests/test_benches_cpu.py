@@ -63,7 +63,7 @@ def test_bench_py_contract_two_ranks():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_port()), str(REPO / "bench.py"),
                         "--gpus", "2", "--steps", "1", "--warmup", "1", "--model", "cifarnet", "--batch", "4",
-                        "--workers-per-gpu", "3", "--f", "1"],
+                        "--workers-per-gpu", "3", "--f", "1", "--full"],
                        capture_output=True, text=True, timeout=600, env=_env())
     assert r.returncode == 0, r.stderr[-3000:]
     rows = _rows(r.stdout)
@@ -112,6 +112,52 @@ def test_bench_py_fp32_and_static_data_modes():
         assert r.returncode == 0, r.stderr[-3000:]
         rows = _rows(r.stdout)
         assert len(rows) == 1 and rows[0]["dtype"] == dtype and word in rows[0]["data"], rows
+
+
+def test_bench_py_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run does the headline job only (no fp32 companion figures; --full adds them), and
+    --dump-outputs writes the last timed step's results as float32 .npy files, the same in every run."""
+    import numpy as np
+
+    args = [sys.executable, str(REPO / "bench.py"), "--steps", "2", "--warmup", "1", "--model", "cifarnet",
+            "--batch", "4", "--workers-per-gpu", "5", "--f", "1"]
+    dumps = []
+    for i in range(2):
+        r = subprocess.run([*args, "--dump-outputs", str(tmp_path / f"d{i}")], capture_output=True, text=True,
+                           timeout=600, env=_env())
+        assert r.returncode == 0, r.stderr[-3000:]
+        rows = _rows(r.stdout)
+        assert len(rows) == 1 and rows[0]["steps"] == 2 and rows[0]["ms_per_step"] > 0
+        assert not [k for k in rows[0] if k.startswith("fp32_")], rows
+        dumps.append({p.stem: np.load(p) for p in sorted((tmp_path / f"d{i}").glob("*.npy"))})
+    assert {"loss", "params", "momentum"} <= set(dumps[0]) and set(dumps[0]) == set(dumps[1])
+    for name, v in dumps[0].items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), name
+        assert np.array_equal(v, dumps[1][name]), name
+    assert dumps[0]["params"].shape == dumps[0]["momentum"].shape and np.abs(dumps[0]["momentum"]).max() > 0
+    r = subprocess.run([*args, "--full"], capture_output=True, text=True, timeout=600, env=_env())
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert _rows(r.stdout)[0]["fp32_ms_per_step"] > 0
+
+
+def test_bench_tuning_table_loads():
+    """bench.py takes its kernel choices from the committed table (no timing in the first step, so two
+    runs compute the same): the file holds every kind of choice and round-trips through ops/tuning.py."""
+    from garfield_amd.ops import grouped, tuning  # noqa: F401  (grouped registers the tables)
+
+    table = json.loads((REPO / "bench_tuning.json").read_text())
+    assert set(table) == {"gemm", "s2", "scwg", "f32conv", "f32wgrad"} and all(table.values())
+    saved = tuning.export()
+    try:
+        tuning.load(table, replace=True)
+        assert tuning.export() == table
+    finally:
+        tuning.load(saved, replace=True)
+        for kind in table:   # load() skips an empty kind: drop what the table put there
+            if not saved.get(kind):
+                tuning._TABLES[kind].clear()
+    src = (REPO / "bench.py").read_text()
+    assert 'setdefault("GARFIELD_TUNING", "fixed")' in src and "bench_tuning.json" in src
 
 
 def test_bench_py_loss_is_a_training_signal():

@@ -1522,6 +1522,71 @@ void g_iwgrad(const at::Tensor& x, const at::Tensor& dy, int64_t kh, int64_t kw,
                              static_cast<int>(splits), out.data_ptr(), bf16, ss, gs, stream_of(x.device()));
 }
 
+// Several wide-kernel 1x1 weight gradients in one launch per 16 jobs. geoms[i]: (kh, kw, sh, sw, ph, pw, dh, dw);
+// outs[i] / splits[i] as gpu_iwgrad's out / splits. Every job is checked like gpu_iwgrad's.
+void g_iwgrad_multi(const std::vector<at::Tensor>& xs, const std::vector<at::Tensor>& dys,
+                    const std::vector<std::vector<int64_t>>& geoms, int64_t groups, const std::vector<at::Tensor>& outs,
+                    const std::vector<int64_t>& splits) {
+  const size_t n = xs.size();
+  TORCH_CHECK(dys.size() == n && geoms.size() == n && outs.size() == n && splits.size() == n,
+              "gpu_iwgrad_multi: xs, dys, geoms, outs and splits must have one entry per job");
+  if (n == 0) return;
+  std::vector<garfield::gpu::WgJob> jobs;
+  jobs.reserve(n);
+  const at::Device dev = xs[0].device();
+  int64_t wgs = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const at::Tensor &x = xs[i], &dy = dys[i], &out = outs[i];
+    const auto& q = geoms[i];
+    TORCH_CHECK(q.size() == 8, "gpu_iwgrad_multi: a geometry is (kh, kw, sh, sw, ph, pw, dh, dw)");
+    TORCH_CHECK(x.device() == dev, "gpu_iwgrad_multi: every job must be on one device");
+    auto g = conv_geometry(x, q[0], q[1], q[2], q[3], q[4], q[5], q[6], q[7]);
+    TORCH_CHECK(dy.is_cuda() && dy.device() == dev && dy.scalar_type() == at::kBFloat16 && dy.dim() == 4 &&
+                    dy.is_contiguous(at::MemoryFormat::ChannelsLast) && dy.size(0) == g.N && dy.size(2) == g.Ho &&
+                    dy.size(3) == g.Wo,
+                "gpu_iwgrad_multi: dy must be a channels_last bf16 [", g.N, ", Cout, ", g.Ho, ", ", g.Wo, "] tensor");
+    const int64_t cout = dy.size(1);
+    TORCH_CHECK(cout <= INT32_MAX && garfield::gpu::iwgrad_wide_ok(g, static_cast<int>(cout)),
+                "gpu_iwgrad_multi: takes 1x1 convolutions with input and output channels multiples of 128 only (got ",
+                g.KH, "x", g.KW, ", ", g.C, " -> ", cout, ")");
+    const int64_t M = static_cast<int64_t>(g.N) * g.Ho * g.Wo;
+    TORCH_CHECK(groups >= 1 && M % groups == 0, "gpu_iwgrad_multi: ", M, " output pixels do not split into ", groups,
+                " workers");
+    TORCH_CHECK(M < INT32_MAX && static_cast<int64_t>(g.N) * g.H * g.W * g.C < INT32_MAX,
+                "gpu_iwgrad_multi: tensor too large");
+    const int64_t S = splits[i];
+    TORCH_CHECK(S >= 1 && S <= 64, "gpu_iwgrad_multi: splits must be in [1, 64]");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(dy.data_ptr()) % 16 == 0,
+                "gpu_iwgrad_multi: x and dy must be 16-byte aligned");
+    const int64_t K = g.C;
+    TORCH_CHECK(out.device() == dev, "gpu_iwgrad_multi: out must be on x's device");
+    bool bf16 = false;
+    int64_t ss = 0, gs = 0;
+    if (out.scalar_type() == at::kFloat) {
+      TORCH_CHECK(out.is_contiguous() && out.dim() == 4 && out.size(0) == S && out.size(1) == groups &&
+                      out.size(2) == cout && out.size(3) == K,
+                  "gpu_iwgrad_multi: an fp32 out must be contiguous [splits, groups, Cout, K]");
+      ss = groups * cout * K;
+      gs = cout * K;
+    } else {
+      TORCH_CHECK(out.scalar_type() == at::kBFloat16 && S == 1 && out.dim() == 3 && out.size(0) == groups &&
+                      out.size(1) == cout && out.size(2) == K && out.stride(2) == 1 && out.stride(1) == K &&
+                      out.stride(0) >= cout * K,
+                  "gpu_iwgrad_multi: a bf16 out must be a [groups, Cout, K] view with contiguous rows (splits == 1)");
+      bf16 = true;
+      gs = out.stride(0);
+    }
+    const int64_t rg = M / groups;
+    wgs += (g.C / 128) * (cout / 128) * groups * S;
+    TORCH_CHECK(wgs < INT32_MAX, "gpu_iwgrad_multi: too many workgroups");
+    jobs.push_back(garfield::gpu::WgJob{u16(x), u16(dy), out.data_ptr(), rg, (rg + S - 1) / S, ss, gs, g,
+                                       static_cast<int>(cout), static_cast<int>(groups), static_cast<int>(S),
+                                       bf16 ? 1 : 0});
+  }
+  c10::hip::HIPGuard guard(dev.index());
+  garfield::gpu::iwgrad_wide_multi(jobs.data(), static_cast<int>(jobs.size()), stream_of(dev));
+}
+
 bool g_wgrad3x3_fits(int64_t n, int64_t h, int64_t w, int64_t c, int64_t cout, int64_t groups) {
   garfield::gpu::Im2col g{static_cast<int>(n), static_cast<int>(h), static_cast<int>(w), static_cast<int>(c), 3, 3,
                           1, 1, 1, 1, 1, 1, static_cast<int>(h), static_cast<int>(w), 0};
@@ -2188,6 +2253,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Pixel fragments per wave the halo-staged 3x3 kernel uses for this NHWC shape (0: it does not fit)");
   m.def("wgrad3x3_fits", &g_wgrad3x3_fits, py::arg("n"), py::arg("h"), py::arg("w"), py::arg("c"), py::arg("cout"),
         py::arg("groups"), "True when gpu_iwgrad of this 3x3 / stride-1 / pad-1 shape runs the halo-staged kernel");
+  m.def("gpu_iwgrad_multi", &g_iwgrad_multi, py::arg("xs"), py::arg("dys"), py::arg("geoms"), py::arg("groups"),
+        py::arg("outs"), py::arg("splits"),
+        "gpu_iwgrad of several 1x1 layers (input and output channels multiples of 128, no prologue) in one "
+        "launch per 16 jobs; every job's result is bitwise what gpu_iwgrad writes for it");
   m.def("gpu_iwgrad", &g_iwgrad, "Per-worker implicit-GEMM weight gradient on MFMA: out[s, g] = Σ over pixel "
         "split s of worker g of dyᵀ · patches(x); args (x, dy, kh, kw, sh, sw, ph, pw, dh, dw, groups, out, splits, "
         "pro_scale=None, pro_shift=None); pro_*: [groups, C] BatchNorm prologue of x (1x1 only)",

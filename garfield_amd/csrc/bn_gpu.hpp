@@ -220,6 +220,26 @@ int iwgrad_taps_per_block(int kw, int kh = 3, int C = 0, int Cout = 0);
 void iwgrad_nhwc(const uint16_t* x, const uint16_t* dy, const Im2col& g, int Cout, int groups, int64_t rg,
                  int splits, void* out, bool out_bf16, int64_t split_stride, int64_t group_stride, hipStream_t stream,
                  const float* pro_scale = nullptr, const float* pro_shift = nullptr);
+// Several weight gradients of the 128 x 128-tile 1x1 kernel (iwgrad_wide_ok: 1x1, C % 128 == 0,
+// Cout % 128 == 0; no prologue) in one launch per kWgJobs jobs: layers whose own grids cannot fill the chip
+// share it. Each job computes exactly what iwgrad_nhwc computes for it (same tiles, same summation order).
+struct WgJob {
+  const uint16_t* x;
+  const uint16_t* dy;
+  void* out;
+  int64_t rg, per_split, split_stride, group_stride;
+  Im2col g;
+  int Cout, groups, splits;
+  int out_bf16;   // out: bf16 row view (splits == 1), else fp32 slabs
+};
+constexpr int kWgJobs = 16;
+struct WgJobs {
+  WgJob j[kWgJobs];
+  int start[kWgJobs];   // first linear workgroup id of each job
+  int n;
+};
+bool iwgrad_wide_ok(const Im2col& g, int Cout);
+void iwgrad_wide_multi(const WgJob* jobs, int count, hipStream_t stream);
 // accumulate: dx += col2im(dcol) instead of dx = col2im(dcol).
 void col2im_nhwc(const uint16_t* dcol, const Im2col& g, uint16_t* dx, bool accumulate, hipStream_t stream);
 

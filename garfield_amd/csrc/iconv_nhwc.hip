@@ -24,7 +24,9 @@
 // channels; grid (ceil(M / (64*PM)), Cout / 64). Requires C % 32 == 0 and
 // Cout % 64 == 0 (checked by the host wrapper). Out-of-range taps read a clamped
 // in-bounds address and are zeroed in registers (no branch around the load).
+#include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "bn_gpu.hpp"
 #include "gar_device.hpp"
@@ -1009,19 +1011,21 @@ constexpr int kW1Stage = 4 * 64 * 128;   // bytes per stage: dy0 | dy1 | x0 | x1
 // stages, where a workgroup's whole K loop is shorter than the load latency the third stage hides:
 // ResNet-50 CIFAR layer4, 10.9-21.8 vs 13.6-26.3 us per call, profiles/r6/iwgrad_wide/). (A 16-byte
 // LDS-staged epilogue measured no faster than the 2-byte stores, which merge in L2.)
-template <bool OUT_BF16, bool PRO, int NS = 3>
-__global__ __launch_bounds__(256) void k_iwgrad_1x1_wide(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy,
-                                                         Im2col g, int Cout, int64_t rg, int64_t per_split, void* out,
-                                                         int64_t split_stride, int64_t group_stride,
-                                                         const float* __restrict__ psc, const float* __restrict__ psh) {
+// The workgroup body: tile (input-channel block fastest) of worker gi's split sp. out_bf16 is a
+// compile-time constant in the single-job kernel and a per-job (wave-uniform) value in the multi-job one.
+template <bool PRO, int NS>
+__device__ __forceinline__ void iwgrad_wide_body(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy,
+                                                 const Im2col& g, int Cout, int64_t rg, int64_t per_split, void* out,
+                                                 bool out_bf16, int64_t split_stride, int64_t group_stride,
+                                                 const float* __restrict__ psc, const float* __restrict__ psh,
+                                                 int tile, int gi, int sp) {
   constexpr int SUB = 64 * 128;          // one [64 px][64 ch] sub-tile
   extern __shared__ __attribute__((aligned(16))) char wlds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int K = g.C;
   const int nq = g.C / 128;
-  const int qb = blockIdx.x % nq, cb = blockIdx.x / nq;
+  const int qb = tile % nq, cb = tile / nq;
   const int c0 = qb * 128, co0 = cb * 128;
-  const int gi = blockIdx.y, sp = blockIdx.z;
   const int64_t mbeg = static_cast<int64_t>(gi) * rg + static_cast<int64_t>(sp) * per_split;
   int64_t mend = mbeg + per_split;
   if (mend > static_cast<int64_t>(gi + 1) * rg) mend = static_cast<int64_t>(gi + 1) * rg;
@@ -1142,19 +1146,50 @@ __global__ __launch_bounds__(256) void k_iwgrad_1x1_wide(const uint16_t* __restr
     }
   }
 
+  auto store = [&](auto bf) {
 #pragma unroll
-  for (int u = 0; u < 4; ++u)
+    for (int u = 0; u < 4; ++u)
 #pragma unroll
-    for (int v = 0; v < 4; ++v)
+      for (int v = 0; v < 4; ++v)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int co = co0 + (4 * sa + u) * 16 + 4 * grp + e;
-        const int k = c0 + (4 * sbk + v) * 16 + li;
-        const int64_t o = static_cast<int64_t>(sp) * split_stride + static_cast<int64_t>(gi) * group_stride +
-                          static_cast<int64_t>(co) * K + k;
-        if constexpr (OUT_BF16) static_cast<uint16_t*>(out)[o] = f_to_bf16(acc[u][v][e]);
-        else static_cast<float*>(out)[o] = acc[u][v][e];
-      }
+        for (int e = 0; e < 4; ++e) {
+          const int co = co0 + (4 * sa + u) * 16 + 4 * grp + e;
+          const int k = c0 + (4 * sbk + v) * 16 + li;
+          const int64_t o = static_cast<int64_t>(sp) * split_stride + static_cast<int64_t>(gi) * group_stride +
+                            static_cast<int64_t>(co) * K + k;
+          if constexpr (decltype(bf)::value) static_cast<uint16_t*>(out)[o] = f_to_bf16(acc[u][v][e]);
+          else static_cast<float*>(out)[o] = acc[u][v][e];
+        }
+  };
+  if (out_bf16) store(std::true_type{});
+  else store(std::false_type{});
+}
+
+template <bool OUT_BF16, bool PRO, int NS = 3>
+__global__ __launch_bounds__(256) void k_iwgrad_1x1_wide(const uint16_t* __restrict__ x, const uint16_t* __restrict__ dy,
+                                                         Im2col g, int Cout, int64_t rg, int64_t per_split, void* out,
+                                                         int64_t split_stride, int64_t group_stride,
+                                                         const float* __restrict__ psc, const float* __restrict__ psh) {
+  iwgrad_wide_body<PRO, NS>(x, dy, g, Cout, rg, per_split, out, OUT_BF16, split_stride, group_stride, psc, psh,
+                            static_cast<int>(blockIdx.x), static_cast<int>(blockIdx.y), static_cast<int>(blockIdx.z));
+}
+
+// Up to kWgJobs such weight gradients in one launch (1-D grid): a workgroup finds its job by a uniform scan
+// of the jobs' first workgroup ids and decodes (tile, worker, split) in the single-job grid's order, tile
+// fastest. Workgroups are independent (no counters, no hand-off). NS is the launch's ring depth.
+template <int NS>
+__global__ __launch_bounds__(256) void k_iwgrad_1x1_wide_multi(WgJobs jobs) {
+  const int bid = static_cast<int>(blockIdx.x);
+  int j = 0;
+  for (int i = 1; i < jobs.n; ++i)
+    if (bid >= jobs.start[i]) j = i;
+  const WgJob& jb = jobs.j[j];
+  const int tiles = (jb.g.C / 128) * (jb.Cout / 128);
+  const int r = bid - jobs.start[j];
+  const int tile = r % tiles, t = r / tiles;
+  const int gi = t % jb.groups, sp = t / jb.groups;
+  iwgrad_wide_body<false, NS>(jb.x, jb.dy, jb.g, jb.Cout, jb.rg, jb.per_split, jb.out, jb.out_bf16 != 0,
+                              jb.split_stride, jb.group_stride, nullptr, nullptr, tile, gi, sp);
 }
 
 // Taps per weight-gradient workgroup: a 3x3 kernel's row of three taps shares each staged dy tile
@@ -1229,6 +1264,44 @@ void iwgrad_launch(const uint16_t* x, const uint16_t* dy, const Im2col& g, int C
   else
     hipLaunchKernelGGL((k_iwgrad<3, false, PRO>), grid, dim3(256), 0, stream, x, dy, g, Cout, rg, per_split, out,
                        split_stride, group_stride, psc, psh);
+}
+
+bool iwgrad_wide_ok(const Im2col& g, int Cout) {
+  return g.KH == 1 && g.KW == 1 && g.C % 128 == 0 && Cout % 128 == 0;
+}
+
+void iwgrad_wide_multi(const WgJob* jobs, int count, hipStream_t stream) {
+  static bool once = (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iwgrad_1x1_wide_multi<3>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 3 * kW1Stage),
+                      hipFuncSetAttribute(reinterpret_cast<const void*>(&k_iwgrad_1x1_wide_multi<2>),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kW1Stage),
+                      true);
+  (void)once;
+  for (int b = 0; b < count; b += kWgJobs) {
+    const int n = count - b < kWgJobs ? count - b : kWgJobs;
+    int order[kWgJobs];
+    int64_t steps[kWgJobs];
+    for (int i = 0; i < n; ++i) {
+      order[i] = i;
+      steps[i] = (jobs[b + i].per_split + 63) / 64;
+    }
+    // long jobs first (their workgroups start early; the short ones fill the tail), stable
+    std::stable_sort(order, order + n, [&](int a, int c) { return steps[a] > steps[c]; });
+    WgJobs wj{};
+    int64_t total = 0;
+    bool ns2 = true;
+    for (int i = 0; i < n; ++i) {
+      const WgJob& jb = jobs[b + order[i]];
+      wj.j[i] = jb;
+      wj.start[i] = static_cast<int>(total);
+      total += static_cast<int64_t>(jb.g.C / 128) * (jb.Cout / 128) * jb.groups * jb.splits;
+      ns2 = ns2 && steps[order[i]] <= 4;
+    }
+    wj.n = n;
+    const dim3 grid(static_cast<unsigned>(total));   // < 2^31: bounded by the host wrapper
+    if (ns2) hipLaunchKernelGGL(k_iwgrad_1x1_wide_multi<2>, grid, dim3(256), 2 * kW1Stage, stream, wj);
+    else hipLaunchKernelGGL(k_iwgrad_1x1_wide_multi<3>, grid, dim3(256), 3 * kW1Stage, stream, wj);
+  }
 }
 
 void iwgrad_nhwc(const uint16_t* x, const uint16_t* dy, const Im2col& g, int Cout, int groups, int64_t rg,

@@ -99,6 +99,19 @@ FOLD_SHORTCUT_BN = True
 # ... and its backward shares one statistics pass and one apply pass with the last BatchNorm's (a ReLU-bit
 # mask or none; tests set False to run the two-call form, which a saved ReLU output still takes)
 BN_DUAL = True
+# 1x1 weight gradients of the 128 x 128-tile kernel whose own grid cannot fill the chip (below
+# _WGRAD_BATCH_MAXWG workgroups: ResNet-50 CIFAR layer2 / layer3, 128-256 workgroups each) are queued in the
+# GradSink and launched together (gpu_iwgrad_multi): nothing reads a weight gradient before the split sums /
+# bucket marks / the flush, where the queue is emptied. Same tiles, same summation order: bitwise the
+# one-by-one results. ResNet-50 CIFAR 5.33-5.35 -> 5.22-5.23 ms/step, 367 -> 347 launches
+# (profiles/r7/wgrad_batch/).
+WGRAD_BATCH = True
+# ImageNet-shape layers reach this with their splits and launch at once; so do layer4's 512-workgroup
+# calls, which batched measure slower than one by one (104.7 vs 113.3 us for the seven)
+_WGRAD_BATCH_MAXWG = 2 * 256
+# queued workgroups at which the queue is launched; 0: when the backward leaves a ResNet stage (x / dy are
+# held for one stage at most). 1536 measured the same within the run-to-run spread (5.210-5.233 ms)
+_WGRAD_BATCH_FLUSH_WG = 0
 
 
 def rows2d(t: torch.Tensor) -> torch.Tensor:
@@ -143,6 +156,9 @@ class GradSink:
         self._split_parts: list = []   # deferred split-K sums (part [S, G, ...] fp32, out [G, ...] rows)
         self._split_outs: list = []
         self.defer_splits = True
+        self._wq: list = []            # deferred 1x1 weight gradients: (x, dy, geometry, out, splits)
+        self._wq_wgs = 0
+        self._wq_stage = None
 
     def offset(self, p: torch.Tensor) -> int:
         return self.offsets[id(p)]
@@ -186,8 +202,31 @@ class GradSink:
         for g in range(self.groups):
             self.put(p, g, grads[g])
 
+    def queue_wgrad(self, x: torch.Tensor, dy: torch.Tensor, geom: tuple, out: torch.Tensor, splits: int,
+                    wgs: int, stage=None) -> None:
+        """A 1x1 weight gradient (``gpu_iwgrad(x, dy, *geom, groups, out, splits)`` of ``wgs`` workgroups)
+        deferred until the queue is launched as one grid: at the static policy point
+        (``_WGRAD_BATCH_FLUSH_WG``) and always before the split sums. Holds x, dy and out until then."""
+        if self._wq and not _WGRAD_BATCH_FLUSH_WG and stage != self._wq_stage:
+            self.flush_wgrads()
+        self._wq_stage = stage
+        self._wq.append((x, dy, list(geom), out, splits))
+        self._wq_wgs += wgs
+        if _WGRAD_BATCH_FLUSH_WG and self._wq_wgs >= _WGRAD_BATCH_FLUSH_WG:
+            self.flush_wgrads()
+
+    def flush_wgrads(self) -> None:
+        """Launch the queued weight gradients now."""
+        if self._wq:
+            xs, dys, geoms, outs, splits = (list(c) for c in zip(*self._wq))
+            self._wq.clear()
+            self._wq_wgs = 0
+            _native.native().gpu_iwgrad_multi(xs, dys, geoms, self.groups, outs, splits)
+
     def flush_splits(self) -> None:
-        """Run the queued split-K sums now (one launch), e.g. before a bucket mark."""
+        """Run the queued weight gradients and split-K sums now (one launch each), e.g. before a bucket
+        mark."""
+        self.flush_wgrads()
         if self._split_parts:
             _native.native().gpu_split_reduce_multi(self._split_parts, self._split_outs)
             self._split_parts.clear()
@@ -542,6 +581,7 @@ class ConvSpec:
         self.kernel = tuple(conv.kernel_size)
         self.stride = tuple(conv.stride)
         self.padding = tuple(conv.padding)
+        self.stage = None          # the ResNet stage the layer belongs to (GradSink.queue_wgrad's flush point)
         self.dilation = tuple(conv.dilation)
         self.gemm = (self.kernel == (1, 1) and self.stride == (1, 1) and self.padding == (0, 0)
                      and self.dilation == (1, 1))
@@ -1055,13 +1095,23 @@ def _iwgrad(x: torch.Tensor, dy: torch.Tensor, spec: "ConvSpec", G: int, K: int,
     else:
         S = _iwgrad_splits(rows, (K // 64) * (cout // 64) * G //
                           C_.iwgrad_taps_per_block(spec.kernel[1], spec.kernel[0], x.shape[1], cout))
+    # a wide-kernel job too small to fill the chip joins the sink's queue (launched with its neighbours)
+    wgs = (K // 128) * (cout // 128) * G * S
+    batch = (WGRAD_BATCH and pro is None and spec.kernel == (1, 1) and K % 128 == 0 and cout % 128 == 0
+             and wgs < _WGRAD_BATCH_MAXWG and isinstance(spec.sink, GradSink) and spec.sink.groups == G)
     out = spec.sink.rows_view(spec.conv.weight, (cout, K), dy.dtype) if S == 1 else None
     if out is not None:
-        C_.gpu_iwgrad(x, dy, *_geom(spec), G, out, 1, **pkw)
+        if batch:
+            spec.sink.queue_wgrad(x, dy, _geom(spec), out, 1, wgs, spec.stage)
+        else:
+            C_.gpu_iwgrad(x, dy, *_geom(spec), G, out, 1, **pkw)
         return
     part = torch.empty((S, G, cout, K), dtype=torch.float32, device=dy.device)
-    C_.gpu_iwgrad(x, dy, *_geom(spec), G, part, S, **pkw)
     rows = spec.sink.rows_view(spec.conv.weight, (cout, K), spec.sink.flat.dtype)
+    if batch and rows is not None and spec.sink.defer_splits:   # (its sum is deferred further: flush_splits)
+        spec.sink.queue_wgrad(x, dy, _geom(spec), part, S, wgs, spec.stage)
+    else:
+        C_.gpu_iwgrad(x, dy, *_geom(spec), G, part, S, **pkw)
     if rows is not None:     # the S slabs summed straight into the exchange rows (deferred, batched)
         spec.sink.queue_split(part, rows)
     else:

@@ -105,6 +105,10 @@ class GroupedResNet:
         self.loss_fn = loss_fn
         self.ws = Workspace()
         self.conv = {m: ConvSpec(m, sink, self.groups) for m in model.modules() if isinstance(m, nn.Conv2d)}
+        for name in ("layer1", "layer2", "layer3", "layer4"):
+            for c in getattr(model, name).modules():
+                if isinstance(c, nn.Conv2d):
+                    self.conv[c].stage = name
         self.fc = LinearSpec(model.fc, sink, self.groups)
         self.bn: dict = {}
         self._seed = None

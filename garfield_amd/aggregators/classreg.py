@@ -133,6 +133,15 @@ class TrimmedMeanGAR(_GAR):
     rule_name = "trimmed-mean"
 
 
+class GeoMedGAR(_GAR):
+    """Geometric median (new, absent from the reference); ``iters:<int>`` / ``nu:<float>`` optional."""
+    rule_name = "geomed"
+    defaults = {"iters": 32, "nu": 1e-6}
+
+    def kwargs(self):
+        return {"iters": int(self.args["iters"]), "nu": float(self.args["nu"])}
+
+
 _register = ClassRegister("GAR")
 itemize = _register.itemize
 register = _register.register
@@ -141,5 +150,6 @@ instantiate = _register.instantiate
 for _name, _cls in (("average", AverageGAR), ("average-nan", AverageNaNGAR), ("median", MedianGAR),
                     ("averaged-median", AveragedMedianGAR), ("krum", KrumGAR), ("krum-py", KrumGAR),
                     ("krum-tf", KrumGAR), ("bulyan", BulyanGAR), ("bulyan-py", BulyanGAR),
-                    ("condense", CondenseGAR), ("trimmed-mean", TrimmedMeanGAR)):
+                    ("condense", CondenseGAR), ("trimmed-mean", TrimmedMeanGAR),
+                    ("geomed", GeoMedGAR)):
     register(_name, _cls)

@@ -23,7 +23,7 @@ import torch
 from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
-         "average-nan"]
+         "average-nan", "geomed"]
 
 
 def default_f(rule: str, n: int) -> int | None:

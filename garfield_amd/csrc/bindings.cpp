@@ -1967,6 +1967,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("m"), py::arg("weights"), py::arg("order"),
      py::arg("scores"), py::arg("batch") = 1,
      "Multi-Krum selection weights on device; batch > 1: gram [batch, np, np] -> weights [batch, n]");
+  m.def("gpu_geomed_select", [](const at::Tensor& gram, int n, int iters, double nu, const at::Tensor& w,
+                                const at::Tensor& dists, int batch) {
+    c10::hip::HIPGuard guard(gram.device().index());
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_geomed_select: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(iters >= 1 && nu > 0.0, "gpu_geomed_select: iters >= 1 and nu > 0");
+    TORCH_CHECK(batch >= 1, "batch must be >= 1");
+    TORCH_CHECK(gram.is_cuda() && w.is_cuda() && dists.is_cuda(), "gpu_geomed_select: GPU tensors expected");
+    const int np = garfield::gpu::gram_padded(n);
+    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && w.numel() >= static_cast<int64_t>(batch) * n &&
+                    dists.numel() >= static_cast<int64_t>(batch) * n,
+                "gpu_geomed_select: buffers too small for the batch");
+    garfield::gpu::geomed_select(fptr(gram), np, n, iters, nu, fptr(w), fptr(dists), stream_of(gram.device()), batch);
+  }, py::arg("gram"), py::arg("n"), py::arg("iters"), py::arg("nu"), py::arg("weights"), py::arg("dists"),
+     py::arg("batch") = 1,
+     "Geometric-median weights (smoothed Weiszfeld on the Gram's distances) on device; dists = the iterate's "
+     "distance to every row; batch > 1: gram [batch, np, np] -> weights / dists [batch, n]");
   def_rows(m, "gpu_lw_gram",
            [](const at::Tensor& G, const at::Tensor& jobs, const at::Tensor& seg_lo, const at::Tensor& slabs,
               const at::Tensor& gram) { g_lw_gram(rows_from_2d(G, true), jobs, seg_lo, slabs, gram); },
@@ -2603,6 +2619,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const int64_t n = dists.numel();
     return weights_tensor(garfield::cpu::aksel_weights(dist_from(dists), n, c), {n});
   });
+  m.def("cpu_geomed_weights", [](const at::Tensor& D, int iters, double nu) {
+    TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_geomed_weights: D must be [n, n]");
+    TORCH_CHECK(iters >= 1 && nu > 0.0, "cpu_geomed_weights: iters >= 1 and nu > 0");
+    const int64_t n = D.size(0);
+    return weights_tensor(garfield::cpu::geomed_weights(dist_from(D), n, iters, nu), {n});
+  }, py::arg("D"), py::arg("iters") = 32, py::arg("nu") = 1e-6,
+     "Geometric-median (smoothed Weiszfeld) weights from squared distances (fp32 [n])");
   m.def("cpu_num_threads", [] { return garfield::cpu::pool().size(); });
 
   garfield::mailbox::bind(m);

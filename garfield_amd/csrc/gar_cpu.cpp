@@ -102,6 +102,50 @@ std::vector<float> krum_weights(const std::vector<double>& D, size_t n, size_t f
   return w;
 }
 
+// Smoothed Weiszfeld on the distance matrix alone (docs/GAR_SEMANTICS.md "Geometric median"):
+// exactly `iters` rounds, every sum in index order over the valid rows.
+std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t iters, double nu) {
+  std::vector<char> valid(n, 0);
+  size_t nv = 0;
+  for (size_t i = 0; i < n; ++i) {
+    for (size_t j = 0; j < n; ++j)
+      if (j != i && std::isfinite(D[i * n + j])) valid[i] = 1;
+    nv += valid[i];
+  }
+  if (nv == 0) return std::vector<float>(n, 1.f / static_cast<float>(n));
+  auto dist = [&](size_t i, size_t j) {
+    const double v = D[i * n + j];
+    return (i != j && std::isfinite(v)) ? v : 0.0;
+  };
+  std::vector<double> a(n, 0.0), s(n, 0.0), b(n, 0.0);
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i]) a[i] = 1.0 / static_cast<double>(nv);
+  for (size_t it = 0; it < iters; ++it) {
+    for (size_t i = 0; i < n; ++i) {
+      if (!valid[i]) continue;
+      double acc = 0.0;
+      for (size_t j = 0; j < n; ++j)
+        if (valid[j]) acc += a[j] * dist(i, j);
+      s[i] = acc;
+    }
+    double q = 0.0;
+    for (size_t i = 0; i < n; ++i)
+      if (valid[i]) q += a[i] * s[i];
+    q *= 0.5;
+    double tot = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+      if (!valid[i]) continue;
+      b[i] = 1.0 / std::max(std::sqrt(std::max(s[i] - q, 0.0)), nu);
+      tot += b[i];
+    }
+    for (size_t i = 0; i < n; ++i)
+      if (valid[i]) a[i] = b[i] / tot;
+  }
+  std::vector<float> w(n, 0.f);
+  for (size_t i = 0; i < n; ++i) w[i] = static_cast<float>(a[i]);
+  return w;
+}
+
 std::vector<float> bulyan_weights(const std::vector<double>& D, size_t n, size_t f, size_t m, size_t t) {
   const size_t q = n - f - 2;
   std::vector<double> scores(n, 0.0);

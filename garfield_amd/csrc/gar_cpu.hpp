@@ -31,6 +31,9 @@ std::vector<float> krum_weights(const std::vector<double>& D, size_t n, size_t f
 std::vector<float> bulyan_weights(const std::vector<double>& D, size_t n, size_t f, size_t m, size_t t);
 std::vector<float> brute_weights(const std::vector<double>& D, size_t n, size_t f);
 std::vector<float> aksel_weights(const std::vector<double>& dists, size_t n, size_t c);
+// Geometric median (smoothed Weiszfeld, `iters` rounds on D alone): rows without a finite
+// off-diagonal distance get weight 0; none valid -> uniform 1/n.
+std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t iters, double nu);
 
 // out = Σ_j w[j] g_j (accumulated in double)
 template <class T> void combine(const Rows<T>& r, const std::vector<float>& w, T* out);

@@ -180,6 +180,24 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// Squared distances D (LDS, pitch n + 1) from a Gram matrix (pitch np) by the whole workgroup:
+// non-finite -> +inf, clamped at 0, `diag` on the diagonal. Shared by the one-workgroup selections.
+__device__ __forceinline__ void fill_distances(const float* __restrict__ gram, int np, int n, float* D,
+                                               float diag = kInf) {
+  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
+    const int i = e / n, j = e % n;
+    float v;
+    if (i == j) {
+      v = diag;
+    } else {
+      v = gram[i * np + i] + gram[j * np + j] - 2.f * gram[i * np + j];
+      if (!isfinite(v)) v = kInf;
+      v = fmaxf(v, 0.f);
+    }
+    D[i * (n + 1) + j] = v;
+  }
+}
+
 __device__ __forceinline__ int score_rank(const float* s, int n, int i) {
   const float si = sanitize_inf(s[i]);
   int rank = 0;

@@ -28,6 +28,12 @@ void gram(const RowTable& rows, int n, int64_t d, int dt, float* slabs, int grid
 void krum_select(const float* gram, int np, int n, int f, int m, float* weights,
                  int* order, float* scores, hipStream_t stream, int batch = 1);
 
+// Geometric median (gar_geomed.hip): `iters` smoothed-Weiszfeld rounds on the distances of the Gram
+// (n <= kMaxRows); weights[n] = the iterate's coefficients, dists[n] = its distance r_i to every row
+// (+inf on rows without a finite distance). batch as krum_select.
+void geomed_select(const float* gram, int np, int n, int iters, double nu, float* weights, float* dists,
+                   hipStream_t stream, int batch = 1);
+
 // W[t][n]: row k = uniform weights of the (m-k) best-scoring gradients at step k
 // batch > 1: gram [batch][np][np] -> W [batch][t][n]
 void bulyan_select(const float* gram, int np, int n, int f, int m, int t, float* W,

@@ -195,21 +195,7 @@ __global__ __launch_bounds__(256) void k_gram_reduce(const float* __restrict__ s
 // (D_ik, k) < (D_ij, j)}, which gives a strict total order, hence the same
 // selection on every rank of a data-parallel job and on the CPU oracle.
 
-// D (pitch n+1) from the Gram; diagonal = +inf, non-finite = +inf, clamped at 0.
-__device__ void fill_distances(const float* __restrict__ gram, int np, int n, float* D) {
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    const int i = e / n, j = e % n;
-    float v;
-    if (i == j) {
-      v = kInf;
-    } else {
-      v = gram[i * np + i] + gram[j * np + j] - 2.f * gram[i * np + j];
-      if (!isfinite(v)) v = kInf;
-      v = fmaxf(v, 0.f);
-    }
-    D[i * (n + 1) + j] = v;
-  }
-}
+// D (pitch n+1) from the Gram: fill_distances (gar_device.hpp), +inf on the diagonal.
 
 // Krum score of row i (sum of the q smallest off-diagonal distances); when
 // keep != nullptr, also reports whether column j is among the q nearest.

@@ -18,7 +18,8 @@ from garfield_amd import aggregators
 
 _RULES = {"Average": "average", "Median": "median", "Krum": "krum", "Brute": "brute", "Aksel": "aksel",
           "Condense": "condense", "Bulyan": "bulyan", "TrimmedMean": "trimmed-mean",
-          "AverageNan": "average-nan", "AveragedMedian": "averaged-median"}
+          "AverageNan": "average-nan", "AveragedMedian": "averaged-median",
+          "GeoMed": "geomed"}
 
 
 class Aggregator_tf:

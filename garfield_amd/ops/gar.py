@@ -9,6 +9,7 @@ GPU path (``garfield_amd._C``, gfx950 HIP), all launches asynchronous on the
 current stream, nothing copied to the host:
 
 * Krum / Multi-Krum: split-K MFMA Gram -> one-workgroup selection -> combine;
+* Geometric median: Gram -> one-workgroup smoothed Weiszfeld on the n x n distances -> combine;
 * Bulyan: Gram -> on-device selection loop -> W[t, n] -> fused W·G averaged-median;
 * Brute: Gram -> device-wide subset search (atomicMin on (diameter, rank)) -> combine;
 * Median / Trimmed-Mean / Averaged-Median / Average-NaN / Condense: register
@@ -351,6 +352,35 @@ def _combine_rows(rows: Rows, w: torch.Tensor) -> torch.Tensor:
     return _finish(C.cpu_combine(rows.obj, w), rows)
 
 
+def geomed_weights(gradients, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
+    """Weights of the geometric median ([n] fp32 on the gradients' device): ``iters`` rounds of
+    smoothed Weiszfeld (RFA) iterated on the pairwise distances alone."""
+    return _geomed_w(prepare(gradients), iters, nu)
+
+
+def _geomed_w(rows: Rows, iters: int, nu: float) -> torch.Tensor:
+    if rows.n > MAX_ROWS:   # the Gram's own device: large_gram on the GPU, no host round trip
+        return geomed_weights_from_gram(_large_gram(rows), iters, nu)
+    C = _C_for(rows)
+    if rows.device.type == "cuda":
+        ws = workspace(rows)
+        g = _gram_into(C, rows, ws)
+        w = ws.get("weights", rows.n)
+        dists = ws.get("geomed_dists", rows.n)
+        C.gpu_geomed_select(g, rows.n, iters, nu, w, dists)
+        return w
+    if C is None:
+        return ref.geomed_weights(ref.pairwise_sqdist(rows.stacked()), iters, nu).float()
+    return C.cpu_geomed_weights(C.cpu_pairwise(rows.obj), iters, nu)
+
+
+def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> torch.Tensor:
+    """Geometric median (minimiser of the sum of L2 distances; breakdown point 1/2, so ``f`` only
+    enters the registry's check): Σ_i a_i g_i with the weights of :func:`geomed_weights`."""
+    rows = prepare(gradients)
+    return _combine_rows(rows, _geomed_w(rows, iters, nu))
+
+
 def bulyan_weights(gradients, f: int, m: int | None = None) -> torch.Tensor:
     rows = prepare(gradients)
     m = rows.n - f - 2 if m is None else m
@@ -599,6 +629,28 @@ def krum_weights_from_gram(g: torch.Tensor, f: int, m: int) -> torch.Tensor:
     return w
 
 
+def geomed_weights_from_gram(g: torch.Tensor, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
+    """Geometric-median weights [n] (fp32, g's device) from a Gram matrix (vectorised, any n):
+    reference.geomed_weights with the distances built as the selection kernels build them."""
+    n = g.shape[0]
+    D = distances_from_gram(g).double()
+    D.fill_diagonal_(0.0)
+    fin = torch.isfinite(D)
+    fin.fill_diagonal_(False)
+    valid = fin.any(1)
+    D = torch.where(fin, D, torch.zeros_like(D))
+    nv = valid.sum()
+    # no valid row (n == 1, every pair non-finite): uniform 1/n, without a host branch on device data
+    a = torch.where(valid, 1.0 / nv.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=g.device))
+    for _ in range(iters):
+        s = (D * a[None, :]).sum(1)
+        q = 0.5 * (a * s).sum()
+        b = torch.where(valid, 1.0 / (s - q).clamp(min=0).sqrt().clamp(min=nu), torch.zeros_like(s))
+        a = b / b.sum().clamp(min=torch.finfo(torch.float64).tiny)
+    a = torch.where(nv > 0, a, torch.full_like(a, 1.0 / n))
+    return a.float()
+
+
 def _stable_order(v: torch.Tensor) -> torch.Tensor:
     """Indices by (value, index), NaN last: reference._order."""
     return torch.sort(_nan_inf(v), stable=True).indices
@@ -675,6 +727,7 @@ RULES = {
     "bulyan": bulyan,
     "brute": brute,
     "aksel": aksel,
+    "geomed": geomed,
     "condense": condense,
     "trimmed-mean": trimmed_mean,
     "averaged-median": averaged_median,

@@ -91,6 +91,44 @@ def krum(G, f: int, m: int | None = None) -> torch.Tensor:
     return combine(G, krum_weights(pairwise_sqdist(G), f, m))
 
 
+def geomed_weights(D: torch.Tensor, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
+    """Weights [n] (fp64) of the smoothed-Weiszfeld geometric median, iterated on the squared
+    distances alone (docs/GAR_SEMANTICS.md "Geometric median"): the iterate z = Σ a_j x_j has
+    ||x_i - z||² = Σ_j a_j D_ij - ½ Σ_jk a_j a_k D_jk. Exactly ``iters`` rounds, sums in index order."""
+    D = D.detach().to(device="cpu", dtype=torch.float64)
+    n = D.shape[0]
+    fin = [[i != j and math.isfinite(float(D[i, j])) for j in range(n)] for i in range(n)]
+    V = [i for i in range(n) if any(fin[i])]
+    if not V:
+        return torch.full((n,), 1.0 / n, dtype=torch.float64)
+    dist = [[float(D[i, j]) if fin[i][j] else 0.0 for j in range(n)] for i in range(n)]
+    a = [0.0] * n
+    for i in V:
+        a[i] = 1.0 / len(V)
+    for _ in range(iters):
+        s = {}
+        for i in V:
+            acc = 0.0
+            for j in V:
+                acc += a[j] * dist[i][j]
+            s[i] = acc
+        q = 0.0
+        for i in V:
+            q += a[i] * s[i]
+        q *= 0.5
+        b, tot = {}, 0.0
+        for i in V:
+            b[i] = 1.0 / max(math.sqrt(max(s[i] - q, 0.0)), nu)
+            tot += b[i]
+        for i in V:
+            a[i] = b[i] / tot
+    return torch.tensor(a, dtype=torch.float64)
+
+
+def geomed(G, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
+    return combine(G, geomed_weights(pairwise_sqdist(G), iters, nu))
+
+
 def bulyan_weights(D: torch.Tensor, f: int, m: int | None = None) -> torch.Tensor:
     n = D.shape[0]
     m = n - f - 2 if m is None else m

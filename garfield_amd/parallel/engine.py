@@ -49,10 +49,10 @@ from garfield_amd.utils.profiling import PhaseTimer
 # the first convolution; users may override the variable explicitly.
 os.environ.setdefault("MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_WRW_XDLOPS", "0")
 
-WEIGHTED_RULES = {"average", "krum", "brute", "aksel"}
+WEIGHTED_RULES = {"average", "krum", "brute", "aksel", "geomed"}
 _LP_MODULES = (nn.modules.conv._ConvNd, nn.Linear)
 COORD_RULES = {"median", "trimmed-mean", "averaged-median", "average-nan", "condense", "bulyan"}
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel"}   # per-layer != flat only for distance-based rules
+LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed"}   # per-layer != flat only for distance-based rules
 # Layer-wise Krum as device operations (gar_layerwise.hip: one segmented Gram launch, a batched
 # selection, one segmented combine + SGD); "0" runs the per-segment loop (the reference form).
 LW_DEVICE = os.environ.get("GARFIELD_LW_DEVICE", "1") != "0"
@@ -510,7 +510,11 @@ class RobustDataParallel:
                 gkw["m"] = cfg.m
             if rule == "condense":
                 gkw.setdefault("seed", cfg.seed + self.step_count)
-            g = gar.aggregate(rule, self.G.float(), **gkw).float()
+            if rule == "geomed":   # continuous weights: kept for last_weights, then the rule's own combine
+                self.last_weights = w = self._weights(rule, kw, self.G.float())
+                g = gar.combine(self.G.float(), w).float()
+            else:
+                g = gar.aggregate(rule, self.G.float(), **gkw).float()
             self._sgd_cpu(g, first)
         self.step_count += 1
 
@@ -544,7 +548,8 @@ class RobustDataParallel:
         if cfg.m is not None and rule in ("krum", "bulyan"):
             gkw["m"] = cfg.m
         cuda = self.device.type == "cuda"
-        if cuda and LW_DEVICE and self.n <= gar.MAX_ROWS and (rule == "krum" or (rule == "bulyan" and self.n <= 64)):
+        if cuda and LW_DEVICE and self.n <= gar.MAX_ROWS and (rule in ("krum", "geomed")
+                                                              or (rule == "bulyan" and self.n <= 64)):
             self._layerwise_device(rule, first)
             return
         g = self._gagg if self._gagg is not None else torch.zeros(self.ld, dtype=torch.float32, device=self.device)
@@ -596,7 +601,8 @@ class RobustDataParallel:
                 gram=torch.empty(L * np_ * np_, dtype=torch.float32, device=dev),
                 w=torch.empty((L, n), dtype=torch.float32, device=dev),
                 order=torch.empty((L, n), dtype=torch.int32, device=dev),
-                scores=torch.empty((L, n), dtype=torch.float32, device=dev), L=L)
+                scores=torch.empty((L, n), dtype=torch.float32, device=dev),
+                dists=torch.empty((L, n), dtype=torch.float32, device=dev), L=L)
         n, f = self.n, cfg.f
         m = cfg.m if cfg.m is not None else n - f - 2
         G = self.G[:, : self.d]
@@ -616,7 +622,11 @@ class RobustDataParallel:
                               first)
             self.last_weights = None
             return
-        C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
+        if rule == "geomed":
+            iters, nu = self._geomed_args(cfg.gar_kwargs)
+            C.gpu_geomed_select(lw["gram"], n, iters, nu, lw["w"], lw["dists"], lw["L"])
+        else:
+            C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
         C.gpu_lw_combine_sgd(G, lw["jobs"], lw["seg_off"], 0, lw["w"], self.flat.data[: self.d], self.mom[: self.d],
                              self._shadow, cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
         self.last_weights = lw["w"]
@@ -634,7 +644,14 @@ class RobustDataParallel:
             return gar.krum_weights(G, f, self.cfg.m)
         if rule == "brute":
             return gar.brute_weights(G, f)
+        if rule == "geomed":
+            return gar.geomed_weights(G, *self._geomed_args(kw))
         return gar.aksel_weights(G, f, kw.get("mode", "mid"))
+
+    @staticmethod
+    def _geomed_args(kw: dict) -> tuple:
+        """(iters, nu) of the geometric median from the rule's keyword arguments."""
+        return int(kw.get("iters", 32)), float(kw.get("nu", 1e-6))
 
     def _coordinate(self, rule: str, kw: dict, out: torch.Tensor, G=None) -> None:
         """Coordinate-wise rule (or Bulyan) over ``G`` (default: the [n, d] exchange rows;
@@ -688,6 +705,8 @@ class RobustDataParallel:
                     w = gar.brute_weights(rows, cfg.f)
                 elif cfg.gar == "aksel":
                     w = gar.aksel_weights(rows, cfg.f, cfg.gar_kwargs.get("mode", "mid"))
+                elif cfg.gar == "geomed":
+                    w = gar.geomed_weights(rows, *self._geomed_args(cfg.gar_kwargs))
                 else:
                     w = torch.full((len(rows),), 1.0 / len(rows), device=self.device)
                 self.last_weights = w

@@ -61,8 +61,8 @@ from garfield_amd.parallel.comm import collectives_on, gloo_backend, world1_coll
 from garfield_amd.parallel.rccl import direct_backend
 from garfield_amd.parallel.signals import Handoff
 
-DISTANCE_RULES = {"krum", "brute", "bulyan"}
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel"}
+DISTANCE_RULES = {"krum", "brute", "bulyan", "geomed"}
+LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed"}
 SUPPORTED = DISTANCE_RULES | {"average", "aksel", "median", "trimmed-mean", "averaged-median", "average-nan",
                               "condense"}
 
@@ -78,7 +78,7 @@ def layerwise_device_ok(rule: str, n: int, f: int) -> bool:
         return n - 2 * f - 2 <= 64
     if rule == "brute":
         return n <= 64
-    return True
+    return True   # krum, geomed (batched one-workgroup selections: n <= MAX_ROWS), aksel
 
 
 def shard_pad(world: int, base: int = 64) -> int:
@@ -620,7 +620,7 @@ class ShardedAggregator:
             mats[b.lo] = self._matrix(b)
         if rule == "brute":   # C(n, f) subsets of n > 128 rows: the device search takes n <= 64
             raise ValueError(f"brute: n must be <= 64 on the GPU (n = {n})")
-        if rule in ("krum", "bulyan"):
+        if rule in ("krum", "bulyan", "geomed"):
             total = None
             for b in self.buckets:
                 g = gar.large_gram(mats[b.lo])                  # MFMA, fp32 (gar_large.hip)
@@ -629,6 +629,8 @@ class ShardedAggregator:
             m = cfg.m if cfg.m is not None else n - f - 2
             if rule == "krum":
                 ws = gar.large_select(gs, f, m)
+            elif rule == "geomed":   # vectorised on the Gram's device: no host round trip
+                ws = gar.geomed_weights_from_gram(gs, *e._geomed_args(kw))
             else:
                 W = gar.large_select(gs, f, m, bulyan=True)
                 Wm = torch.empty_like(W)
@@ -686,6 +688,11 @@ class ShardedAggregator:
             order = ws.get("order", n, torch.int32)
             scores = ws.get("scores", n)
             C.gpu_krum_select(gram_total, n, f, m, w, order, scores)
+            return w
+        if rule == "geomed":
+            w = ws.get("weights", n)
+            dists = ws.get("geomed_dists", n)
+            C.gpu_geomed_select(gram_total, n, *self.e._geomed_args(cfg.gar_kwargs), w, dists)
             return w
         if rule == "brute":
             if n > 64:
@@ -746,6 +753,7 @@ class ShardedAggregator:
             plan["w"] = torch.empty((L, n), dtype=torch.float32, device=dev)
             plan["order"] = torch.empty((L, n), dtype=torch.int32, device=dev)
             plan["scores"] = torch.empty((L, n), dtype=torch.float32, device=dev)
+            plan["dists"] = torch.empty((L, n), dtype=torch.float32, device=dev)
             plan["best"] = torch.empty(1, dtype=torch.int64, device=dev)
             plan["np"] = np_
         self._lwp = plan
@@ -828,6 +836,8 @@ class ShardedAggregator:
                     np2 = plan["np"] ** 2
                     for si in range(L):
                         C.gpu_brute_select(total[si * np2:(si + 1) * np2], n, f, plan["best"], plan["w"][si])
+                elif rule == "geomed":
+                    C.gpu_geomed_select(total, n, *e._geomed_args(cfg.gar_kwargs), plan["w"], plan["dists"], L)
                 else:
                     C.gpu_krum_select(total, n, f, m, plan["w"], plan["order"], plan["scores"], L)
             e.last_weights = plan["w"]
@@ -861,6 +871,9 @@ class ShardedAggregator:
                 Ds.fill_diagonal_(math.inf)
                 if rule == "krum":
                     W[si] = ref.krum_weights(Ds, f, m).float()
+                elif rule == "geomed":
+                    ga = e._geomed_args(cfg.gar_kwargs)
+                    W[si] = (Cn.cpu_geomed_weights(Ds, *ga) if Cn is not None else ref.geomed_weights(Ds, *ga)).float()
                 elif rule == "brute":
                     W[si] = (Cn.cpu_brute_weights(Ds, f) if Cn is not None else ref.brute_weights(Ds, f)).float()
                 else:
@@ -925,6 +938,9 @@ class ShardedAggregator:
                 return gar._torch_closest_mean(ref.bulyan_weights(D, f, m).float() @ X, t - 2 * f)
             if rule == "krum":
                 w = C.cpu_krum_weights(D, f, m)[0] if C is not None else ref.krum_weights(D, f, m).float()
+            elif rule == "geomed":
+                ga = e._geomed_args(kw)
+                w = C.cpu_geomed_weights(D, *ga) if C is not None else ref.geomed_weights(D, *ga).float()
             else:
                 w = C.cpu_brute_weights(D, f) if C is not None else ref.brute_weights(D, f).float()
             e.last_weights = w

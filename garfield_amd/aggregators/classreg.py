@@ -142,6 +142,21 @@ class GeoMedGAR(_GAR):
         return {"iters": int(self.args["iters"]), "nu": float(self.args["nu"])}
 
 
+class NNMKrumGAR(KrumGAR):
+    """Multi-Krum after nearest-neighbour mixing over the n - f nearest (new, absent from the reference)."""
+    rule_name = "nnm-krum"
+
+
+class NNMGeoMedGAR(GeoMedGAR):
+    """Geometric median after nearest-neighbour mixing (new, absent from the reference)."""
+    rule_name = "nnm-geomed"
+
+
+class NNMAverageGAR(_GAR):
+    """Average after nearest-neighbour mixing (new, absent from the reference)."""
+    rule_name = "nnm-average"
+
+
 _register = ClassRegister("GAR")
 itemize = _register.itemize
 register = _register.register
@@ -151,5 +166,6 @@ for _name, _cls in (("average", AverageGAR), ("average-nan", AverageNaNGAR), ("m
                     ("averaged-median", AveragedMedianGAR), ("krum", KrumGAR), ("krum-py", KrumGAR),
                     ("krum-tf", KrumGAR), ("bulyan", BulyanGAR), ("bulyan-py", BulyanGAR),
                     ("condense", CondenseGAR), ("trimmed-mean", TrimmedMeanGAR),
-                    ("geomed", GeoMedGAR)):
+                    ("geomed", GeoMedGAR), ("nnm-krum", NNMKrumGAR), ("nnm-geomed", NNMGeoMedGAR),
+                    ("nnm-average", NNMAverageGAR)):
     register(_name, _cls)

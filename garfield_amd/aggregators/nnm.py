@@ -1,0 +1,48 @@
+"""Nearest-neighbour mixing (NNM; Allouah et al., "Fixing by Mixing", AISTATS 2023) in front of a
+rule (new, absent from the reference): every gradient is replaced by the mean of its ``n - f``
+nearest gradients, itself included, then Krum, the geometric median or the average runs on the
+mixed gradients. The mixing is folded into the rule's weights (``docs/GAR_SEMANTICS.md``
+"Nearest-neighbour mixing"): the aggregate is Σ_j w_j g_j over the ORIGINAL gradients."""
+from garfield_amd.aggregators import register
+from garfield_amd.aggregators._common import n_of
+from garfield_amd.aggregators.average import check as _average_check
+from garfield_amd.aggregators.geomed import check as _geomed_check
+from garfield_amd.aggregators.krum import check as _krum_check
+from garfield_amd.ops import gar
+
+
+def _check_mix(gradients, f):
+    n = n_of(gradients)
+    if not isinstance(f, int) or isinstance(f, bool) or not 0 <= f < n:
+        return f"Invalid number of Byzantine gradients to mix out, got f = {f!r}, expected 0 <= f <= {n - 1}"
+    return None
+
+
+def _rule_kwargs(rule, m=None, iters=32, nu=1e-6, **kwargs):
+    return {"krum": {"m": m}, "geomed": {"iters": iters, "nu": nu}, "average": {}}[rule]
+
+
+def _make(rule, own_check):
+    def aggregate(gradients, f=0, **kwargs):
+        return gar.nnm(gradients, f, rule, **_rule_kwargs(rule, **kwargs))
+
+    aggregate.__doc__ = f"{rule} of the gradients mixed over their n - f nearest: Σ_j w_j g_j with the folded weights."
+
+    def check(gradients, f=0, **kwargs):
+        msg = own_check(gradients=gradients, f=f, **kwargs)
+        if msg:
+            return msg
+        return _check_mix(gradients, f)
+
+    def influence(honests, attacks, f=0, **kwargs):
+        """Total weight of the attack gradients (the folded weights are non-zero on nearly every row)."""
+        w = gar.nnm_weights(list(honests) + list(attacks), f, rule, **_rule_kwargs(rule, **kwargs))
+        return float(w.detach().double().cpu()[len(honests):].sum())
+
+    # no variance-to-norm bound is claimed: upper_bound stays None
+    register("nnm-" + rule, aggregate, check, influence=influence)
+
+
+_make("krum", _krum_check)
+_make("geomed", _geomed_check)
+_make("average", _average_check)

@@ -23,7 +23,7 @@ import time
 import torch
 
 from garfield_amd import aggregators
-from garfield_amd.apps.common import StepTimer, add_common, init_rpc, print_setup, seed_all
+from garfield_amd.apps.common import StepTimer, add_common, gar_name, init_rpc, print_setup, seed_all
 from garfield_amd.runtime import tools
 from garfield_amd.runtime.byz_worker import ByzWorker
 from garfield_amd.runtime.server import Server
@@ -40,7 +40,7 @@ def parse(argv=None):
 
 
 def run_server(a, world_size, results: dict | None = None):
-    gar = aggregators.get(a.gar)
+    gar = aggregators.get(gar_name(a))
     ps = Server(a.rank, world_size, a.num_workers, 1, a.fw, a.fps, "worker:", "ps:", a.batch, a.model, a.dataset,
                 a.optimizer, a.train_size, device=a.device, rpc_timeout=a.rpc_timeout, **a.opt_args)
     lr = float(a.opt_args.get("lr", 0.1))

@@ -19,7 +19,7 @@ import time
 import torch
 
 from garfield_amd import aggregators
-from garfield_amd.apps.common import StepTimer, add_common, init_rpc, print_setup, seed_all
+from garfield_amd.apps.common import StepTimer, add_common, gar_name, init_rpc, print_setup, seed_all
 from garfield_amd.runtime.byz_server import ByzServer
 from garfield_amd.runtime.byz_worker import ByzWorker
 from garfield_amd.runtime.server import Server
@@ -37,7 +37,7 @@ def parse(argv=None):
 
 
 def run_server(a, world_size, results: dict | None = None):
-    gar = aggregators.get(a.gar)
+    gar = aggregators.get(gar_name(a))
     mar = aggregators.get(a.mar or (a.gar if a.fps > 0 else "average"))
     args = (a.rank, world_size, a.num_workers, a.num_ps, a.fw, a.fps, "worker:", "ps:", a.batch, a.model, a.dataset,
             a.optimizer)

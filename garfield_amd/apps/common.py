@@ -43,6 +43,9 @@ def add_common(p: argparse.ArgumentParser, ps: bool = True) -> argparse.Argument
                    help='Optimizer arguments as JSON, e.g. \'{"lr":"0.1"}\'')
     p.add_argument("--num_iter", type=int, default=5000)
     p.add_argument("--gar", type=str, default="average")
+    p.add_argument("--pre_aggregation", type=str, default=None, choices=["nnm"],
+                   help="nnm: nearest-neighbour mixing before --gar (krum, geomed, average): every gradient is "
+                        "replaced by the mean of its n - f nearest, for heterogeneous (--non_iid) data")
     p.add_argument("--acc_freq", type=int, default=100, help="Accuracy evaluation period (iterations).")
     p.add_argument("--bench", type=str2bool, default=False, help="Print per-step timing and bandwidth.")
     p.add_argument("--log", type=str2bool, default=False, help="Print the loss at each iteration.")
@@ -52,6 +55,12 @@ def add_common(p: argparse.ArgumentParser, ps: bool = True) -> argparse.Argument
     p.add_argument("--device", type=str, default=None, help="cpu / cuda (default: cuda when available)")
     p.add_argument("--rpc_timeout", type=float, default=600.0)
     return p
+
+
+def gar_name(a) -> str:
+    """The registry name of ``--gar`` with ``--pre_aggregation`` applied (``nnm-krum``, ...)."""
+    pre = getattr(a, "pre_aggregation", None)
+    return f"{pre}-{a.gar}" if pre else a.gar
 
 
 def print_setup(rank: int, **fields) -> None:

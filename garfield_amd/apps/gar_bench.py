@@ -23,10 +23,12 @@ import torch
 from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
-         "average-nan", "geomed"]
+         "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average"]
 
 
 def default_f(rule: str, n: int) -> int | None:
+    if rule.startswith("nnm-"):   # the f of the plain rule (average: as geomed), so the pair is comparable
+        rule = "geomed" if rule == "nnm-average" else rule[4:]
     if rule in ("average", "average-nan", "median"):
         return None
     if rule == "bulyan":
@@ -82,7 +84,7 @@ def main(argv=None):
             inp = [G[i].clone() for i in range(n)] if a.list_input else G
             for rule in a.rules:
                 f = default_f(rule, n)
-                if rule in ("krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense") and f is None:
+                if rule in ("krum", "nnm-krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense") and f is None:
                     continue
                 if rule == "brute" and n > 20:
                     continue

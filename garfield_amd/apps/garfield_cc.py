@@ -70,6 +70,8 @@ def parse(argv=None):
     p.add_argument("--lr_gamma", type=float, default=0.1)
     p.add_argument("--num_iter", type=int, default=0, help="stop after this many iterations (0: epochs)")
     p.add_argument("--aggregator", default="vanilla", help="GAR name; vanilla = average (reference default)")
+    p.add_argument("--pre_aggregation", default=None, choices=["nnm"],
+                   help="nnm: nearest-neighbour mixing before --aggregator (krum, geomed, average)")
     p.add_argument("--mar", default="median")
     p.add_argument("--attack", default="", help="attack of the fw Byzantine worker slots")
     p.add_argument("--ps_attack", default="", help="attack of the fps Byzantine servers")
@@ -131,6 +133,8 @@ def main(argv=None, results: dict | None = None):
                   exchange_dtype=xdt, byzantine=byz, cuda_graph=a.cuda_graph)
     if a.layerwise:
         common.update(layerwise=True)
+    if a.pre_aggregation:
+        common.update(pre_aggregation=a.pre_aggregation)
     if byz_mode:
         eng = ByzantinePSDataParallel(model, loss_fn, ctx,
                                       ByzPSConfig(num_ps=a.num_ps, fps=a.fps, mar=mar, ps_attack=a.ps_attack,

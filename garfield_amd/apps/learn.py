@@ -15,7 +15,7 @@ import sys
 import time
 
 from garfield_amd import aggregators
-from garfield_amd.apps.common import StepTimer, add_common, init_rpc, print_setup, seed_all
+from garfield_amd.apps.common import StepTimer, add_common, gar_name, init_rpc, print_setup, seed_all
 from garfield_amd.runtime.byz_worker import ByzWorker
 from garfield_amd.runtime.server import Server
 from garfield_amd.runtime.worker import Worker
@@ -56,7 +56,7 @@ def main(argv=None, results: dict | None = None, progress=None):
     if a.collective:
         return _main_collective(a, results, progress)
     init_rpc(f"node:{a.rank}", a.rank, n, a.master, a.port, a.rpc_timeout)
-    gar = aggregators.get(a.gar)
+    gar = aggregators.get(gar_name(a))
     if a.attack and a.rank < f:
         ByzWorker(a.rank, n, n, a.batch, a.model, a.dataset, a.loss, a.attack, f, a.train_size, device=a.device)
     else:
@@ -103,7 +103,7 @@ def _main_collective(a, results, progress):
             "LOCAL_RANK", str(a.rank % max(torch.cuda.device_count(), 1))), MASTER_ADDR=a.master,
             MASTER_PORT=str(a.port))
     ctx = init_distributed(backend=a.backend, device=a.device)
-    node = CollectiveLearnNode(ctx, a.model, a.dataset, a.batch, a.loss, a.optimizer, a.opt_args, a.gar, a.f,
+    node = CollectiveLearnNode(ctx, a.model, a.dataset, a.batch, a.loss, a.optimizer, a.opt_args, gar_name(a), a.f,
                                a.attack, bool(a.non_iid), train_size=a.train_size)
     start = time.time()
     acc = None

@@ -1983,6 +1983,39 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      py::arg("batch") = 1,
      "Geometric-median weights (smoothed Weiszfeld on the Gram's distances) on device; dists = the iterate's "
      "distance to every row; batch > 1: gram [batch, np, np] -> weights / dists [batch, n]");
+  m.def("gpu_nnm_mix", [](const at::Tensor& gram, int n, int f, const at::Tensor& H, const at::Tensor& masks,
+                          int batch) {
+    c10::hip::HIPGuard guard(gram.device().index());
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_nnm_mix: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(f >= 0 && f < n, "gpu_nnm_mix: 0 <= f < n");
+    TORCH_CHECK(batch >= 1, "batch must be >= 1");
+    TORCH_CHECK(gram.is_cuda() && H.is_cuda() && masks.is_cuda(), "gpu_nnm_mix: GPU tensors expected");
+    TORCH_CHECK(masks.scalar_type() == at::kLong && masks.is_contiguous(), "gpu_nnm_mix: masks must be contiguous int64");
+    const int np = garfield::gpu::gram_padded(n);
+    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && H.numel() >= static_cast<int64_t>(batch) * np * np &&
+                    masks.numel() >= static_cast<int64_t>(batch) * 2 * n,
+                "gpu_nnm_mix: buffers too small for the batch");
+    TORCH_CHECK(fptr(gram) != fptr(H), "gpu_nnm_mix: H must not alias the Gram");
+    garfield::gpu::nnm_mix(fptr(gram), np, n, f, fptr(H), reinterpret_cast<unsigned long long*>(masks.data_ptr<int64_t>()),
+                           stream_of(gram.device()), batch);
+  }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("H"), py::arg("masks"), py::arg("batch") = 1,
+     "Nearest-neighbour mixing on the Gram: masks [n, 2] int64 (each row's n - f nearest, itself included) and the "
+     "pseudo-Gram H [np, np] of the mixed rows for the selections; batch > 1: gram [batch, np, np] -> H, masks [batch, n, 2]");
+  m.def("gpu_nnm_unmix", [](const at::Tensor& a, const at::Tensor& masks, int n, int f, const at::Tensor& w, int batch) {
+    c10::hip::HIPGuard guard(a.device().index());
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_nnm_unmix: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(f >= 0 && f < n, "gpu_nnm_unmix: 0 <= f < n");
+    TORCH_CHECK(batch >= 1, "batch must be >= 1");
+    TORCH_CHECK(a.is_cuda() && w.is_cuda() && masks.is_cuda(), "gpu_nnm_unmix: GPU tensors expected");
+    TORCH_CHECK(masks.scalar_type() == at::kLong && masks.is_contiguous(), "gpu_nnm_unmix: masks must be contiguous int64");
+    TORCH_CHECK(a.numel() >= static_cast<int64_t>(batch) * n && w.numel() >= static_cast<int64_t>(batch) * n &&
+                    masks.numel() >= static_cast<int64_t>(batch) * 2 * n,
+                "gpu_nnm_unmix: buffers too small for the batch");
+    TORCH_CHECK(fptr(a) != fptr(w), "gpu_nnm_unmix: w must not alias a");
+    garfield::gpu::nnm_unmix(fptr(a), reinterpret_cast<const unsigned long long*>(masks.data_ptr<int64_t>()), n, f,
+                             fptr(w), stream_of(a.device()), batch);
+  }, py::arg("a"), py::arg("masks"), py::arg("n"), py::arg("f"), py::arg("w"), py::arg("batch") = 1,
+     "Fold weights a [n] over the mixed rows back onto the original rows: w_j = sum of a_i over the sets holding j, / (n - f)");
   def_rows(m, "gpu_lw_gram",
            [](const at::Tensor& G, const at::Tensor& jobs, const at::Tensor& seg_lo, const at::Tensor& slabs,
               const at::Tensor& gram) { g_lw_gram(rows_from_2d(G, true), jobs, seg_lo, slabs, gram); },
@@ -2626,7 +2659,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return weights_tensor(garfield::cpu::geomed_weights(dist_from(D), n, iters, nu), {n});
   }, py::arg("D"), py::arg("iters") = 32, py::arg("nu") = 1e-6,
      "Geometric-median (smoothed Weiszfeld) weights from squared distances (fp32 [n])");
-  m.def("cpu_num_threads", [] { return garfield::cpu::pool().size(); });
+  m.def("cpu_nnm_mix", [](const at::Tensor& D, int f) {
+    TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_nnm_mix: D must be [n, n]");
+    const int64_t n = D.size(0);
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "cpu_nnm_mix: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(f >= 0 && f < n, "cpu_nnm_mix: 0 <= f < n");
+    std::vector<uint64_t> mk;
+    auto Dm = garfield::cpu::nnm_mix(dist_from(D), n, f, &mk);
+    auto out = at::empty({n, n}, at::TensorOptions().dtype(at::kDouble));
+    std::copy(Dm.begin(), Dm.end(), out.data_ptr<double>());
+    auto masks = at::empty({n, 2}, at::TensorOptions().dtype(at::kLong));
+    for (int64_t e = 0; e < 2 * n; ++e) masks.data_ptr<int64_t>()[e] = static_cast<int64_t>(mk[e]);
+    return py::make_tuple(out, masks);
+  }, py::arg("D"), py::arg("f"),
+     "Nearest-neighbour mixing from squared distances: (D' [n, n] fp64 of the mixed rows, masks [n, 2] int64)");
+  m.def("cpu_nnm_unmix", [](const at::Tensor& a, const at::Tensor& masks, int c) {
+    const int64_t n = a.numel();
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "cpu_nnm_unmix: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(c >= 1 && c <= n, "cpu_nnm_unmix: 1 <= c <= n");
+    TORCH_CHECK(masks.scalar_type() == at::kLong && masks.numel() == 2 * n, "cpu_nnm_unmix: masks must be [n, 2] int64");
+    auto mc = masks.contiguous().cpu();
+    std::vector<uint64_t> mk(2 * n);
+    for (int64_t e = 0; e < 2 * n; ++e) mk[e] = static_cast<uint64_t>(mc.data_ptr<int64_t>()[e]);
+    return weights_tensor(garfield::cpu::nnm_unmix(floats_from(a), mk, n, c), {n});
+  }, py::arg("a"), py::arg("masks"), py::arg("c"),
+     "Fold weights over the mixed rows back onto the original rows (fp32 [n])");
+  m.def("cpu_num_threads",[] { return garfield::cpu::pool().size(); });
 
   garfield::mailbox::bind(m);
 }

@@ -146,6 +146,75 @@ std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t
   return w;
 }
 
+// Nearest-neighbour mixing (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing"): the oracle's sums in
+// the oracle's order (set members ascending, the inner sum over l first).
+std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, std::vector<uint64_t>* masks) {
+  const size_t c = n - f;
+  const double inf = std::numeric_limits<double>::infinity();
+  auto d0 = [&](size_t k, size_t l) {
+    const double v = D[k * n + l];
+    return k == l ? 0.0 : (std::isfinite(v) ? v : inf);
+  };
+  std::vector<uint64_t> mk(2 * n, 0);
+  auto has = [&](size_t i, size_t j) { return (mk[2 * i + (j >> 6)] >> (j & 63)) & 1u; };
+  for (size_t i = 0; i < n; ++i) {
+    mk[2 * i + (i >> 6)] |= uint64_t{1} << (i & 63);
+    for (size_t j = 0; j < n; ++j) {
+      if (j == i) continue;
+      const double dj = d0(i, j);
+      size_t rank = 0;
+      for (size_t k = 0; k < n; ++k) {
+        if (k == i) continue;
+        const double dk = d0(i, k);
+        rank += dk < dj || (dk == dj && k < j);
+      }
+      if (rank + 1 < c) mk[2 * i + (j >> 6)] |= uint64_t{1} << (j & 63);
+    }
+  }
+  std::vector<double> R(n * n, 0.0);   // R[j * n + k] = Σ_{l∈S_j} D⁰_kl
+  for (size_t j = 0; j < n; ++j)
+    for (size_t k = 0; k < n; ++k) {
+      double acc = 0.0;
+      for (size_t l = 0; l < n; ++l)
+        if (has(j, l)) acc += d0(k, l);
+      R[j * n + k] = acc;
+    }
+  auto m_of = [&](size_t i, size_t j) {
+    double acc = 0.0;
+    for (size_t k = 0; k < n; ++k)
+      if (has(i, k)) acc += R[j * n + k];
+    return acc / (static_cast<double>(c) * static_cast<double>(c));
+  };
+  std::vector<double> diag(n);
+  for (size_t i = 0; i < n; ++i) diag[i] = m_of(i, i);
+  std::vector<double> out(n * n, inf);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = i + 1; j < n; ++j) {
+      const double mij = m_of(i, j);
+      double v = inf;
+      if (!std::isinf(mij) && !std::isinf(diag[i]) && !std::isinf(diag[j]))
+        v = std::max(mij - 0.5 * diag[i] - 0.5 * diag[j], 0.0);
+      out[i * n + j] = out[j * n + i] = v;
+    }
+  if (masks) *masks = std::move(mk);
+  return out;
+}
+
+std::vector<float> nnm_unmix(const std::vector<float>& a, const std::vector<uint64_t>& masks, size_t n, size_t c) {
+  std::vector<double> acc(n, 0.0);
+  double tot = 0.0;   // the fp32 a sum to 1 only within rounding: w is normalised by their fp64 sum
+  for (size_t i = 0; i < n; ++i) {
+    if (a[i] == 0.f) continue;
+    tot += static_cast<double>(a[i]);
+    for (size_t j = 0; j < n; ++j)
+      if ((masks[2 * i + (j >> 6)] >> (j & 63)) & 1u) acc[j] += static_cast<double>(a[i]);
+  }
+  std::vector<float> w(n, 0.f);
+  if (tot == 0.0) return w;
+  for (size_t j = 0; j < n; ++j) w[j] = static_cast<float>(acc[j] / tot / static_cast<double>(c));
+  return w;
+}
+
 std::vector<float> bulyan_weights(const std::vector<double>& D, size_t n, size_t f, size_t m, size_t t) {
   const size_t q = n - f - 2;
   std::vector<double> scores(n, 0.0);

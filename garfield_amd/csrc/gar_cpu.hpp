@@ -35,6 +35,13 @@ std::vector<float> aksel_weights(const std::vector<double>& dists, size_t n, siz
 // off-diagonal distance get weight 0; none valid -> uniform 1/n.
 std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t iters, double nu);
 
+// Nearest-neighbour mixing on D alone (0 <= f < n, c = n - f; docs/GAR_SEMANTICS.md). nnm_mix: masks[2n]
+// (row i's set, i and its c - 1 nearest, as two 64-bit words; n <= 128) and the squared distances D' of
+// the mixed rows (+inf diagonal), for the selections above. nnm_unmix: the selection's weights a over
+// the mixed rows folded back onto the original rows.
+std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, std::vector<uint64_t>* masks);
+std::vector<float> nnm_unmix(const std::vector<float>& a, const std::vector<uint64_t>& masks, size_t n, size_t c);
+
 // out = Σ_j w[j] g_j (accumulated in double)
 template <class T> void combine(const Rows<T>& r, const std::vector<float>& w, T* out);
 

@@ -34,6 +34,16 @@ void krum_select(const float* gram, int np, int n, int f, int m, float* weights,
 void geomed_select(const float* gram, int np, int n, int iters, double nu, float* weights, float* dists,
                    hipStream_t stream, int batch = 1);
 
+// Nearest-neighbour mixing (gar_nnm.hip), n <= kMaxRows, 0 <= f < n, c = n - f. nnm_mix: from the Gram,
+// masks[n][2] (the set S_i of row i as two 64-bit words: i and its c - 1 nearest) and the pseudo-Gram
+// H [np][np] (H_ii = 0, H_ij = -D'_ij / 2 with D' the squared distances of the mixed rows), on which
+// krum_select / geomed_select run unchanged. nnm_unmix: w[n] = the selection's weights a[n] over the
+// mixed rows folded back onto the original rows (a and w distinct). batch as krum_select.
+void nnm_mix(const float* gram, int np, int n, int f, float* H, unsigned long long* masks, hipStream_t stream,
+             int batch = 1);
+void nnm_unmix(const float* a, const unsigned long long* masks, int n, int f, float* w, hipStream_t stream,
+               int batch = 1);
+
 // W[t][n]: row k = uniform weights of the (m-k) best-scoring gradients at step k
 // batch > 1: gram [batch][np][np] -> W [batch][t][n]
 void bulyan_select(const float* gram, int np, int n, int f, int m, int t, float* W,

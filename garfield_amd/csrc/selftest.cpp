@@ -10,6 +10,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstdio>
+#include <limits>
 #include <random>
 #include <thread>
 #include <vector>
@@ -96,6 +97,40 @@ static void test_gars() {
   cpu::combine<float>(r, w, out.data());
 }
 
+// Nearest-neighbour mixing on a distance matrix of points on a line: rows 0..3 get the same set
+// (exact zero distances), row 6 is non-finite (tainted: it takes no weight).
+static void test_nnm() {
+  const size_t n = 7, f = 2, c = n - f;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double pos[n] = {0.0, 0.1, 1.0, 1.3, 5.0, 5.2, 0.0};
+  std::vector<double> D(n * n, inf);
+  for (size_t i = 0; i + 1 < n; ++i)
+    for (size_t j = 0; j + 1 < n; ++j)
+      if (i != j) D[i * n + j] = (pos[i] - pos[j]) * (pos[i] - pos[j]);
+  std::vector<uint64_t> mk;
+  auto Dm = cpu::nnm_mix(D, n, f, &mk);
+  CHECK(mk.size() == 2 * n);
+  for (size_t i = 0; i < n; ++i) {
+    CHECK((mk[2 * i] >> i) & 1u);
+    CHECK(__builtin_popcountll(mk[2 * i]) == static_cast<int>(c) && mk[2 * i + 1] == 0);
+  }
+  CHECK(mk[0] == 0x1Fu && mk[2] == 0x1Fu);      // rows 0 and 1: {0, 1, 2, 3, 4}
+  CHECK(Dm[0 * n + 1] == 0.0 && Dm[1 * n + 0] == 0.0);
+  CHECK(mk[2 * 5] == 0x3Eu);                    // row 5: {1, 2, 3, 4, 5}
+  // mixed rows on the line: y_0 = 1.48, y_5 = 2.52
+  CHECK(std::fabs(Dm[0 * n + 5] - 1.04 * 1.04) < 1e-12);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < n; ++j) CHECK(Dm[i * n + j] == Dm[j * n + i]);
+  for (size_t j = 0; j + 1 < n; ++j) CHECK(std::isinf(Dm[6 * n + j]));   // the tainted row
+  auto a = cpu::krum_weights(Dm, n, f, n - f - 2);
+  CHECK(a[6] == 0.f);
+  auto w = cpu::nnm_unmix(a, mk, n, c);
+  float tot = 0;
+  for (float x : w) tot += x;
+  CHECK(std::fabs(tot - 1.f) < 1e-6f);
+  CHECK(w[6] == 0.f && w[5] == 0.f && w[0] == 0.2f);
+}
+
 static void test_mailbox() {
   mailbox::Mailbox mb(8, 4096, false);
   std::vector<std::thread> writers;
@@ -119,6 +154,7 @@ static void test_mailbox() {
 int main() {
   test_pool();
   test_gars();
+  test_nnm();
   test_mailbox();
   if (failures) {
     std::fprintf(stderr, "selftest: %d failure(s)\n", failures);

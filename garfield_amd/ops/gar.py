@@ -10,6 +10,8 @@ current stream, nothing copied to the host:
 
 * Krum / Multi-Krum: split-K MFMA Gram -> one-workgroup selection -> combine;
 * Geometric median: Gram -> one-workgroup smoothed Weiszfeld on the n x n distances -> combine;
+* Nearest-neighbour mixing before Krum / geometric median / average: Gram -> one-workgroup mix
+  (neighbour sets + the mixed rows' pseudo-Gram) -> the rule's selection -> un-mix -> combine;
 * Bulyan: Gram -> on-device selection loop -> W[t, n] -> fused W·G averaged-median;
 * Brute: Gram -> device-wide subset search (atomicMin on (diameter, rank)) -> combine;
 * Median / Trimmed-Mean / Averaged-Median / Average-NaN / Condense: register
@@ -305,9 +307,12 @@ def average(gradients, **_) -> torch.Tensor:
     return _finish(rows.stacked().float().mean(0) if rows.dtype != torch.float64 else rows.stacked().mean(0), rows)
 
 
-def krum_weights(gradients, f: int, m: int | None = None) -> torch.Tensor:
-    """Selection weights of Multi-Krum ([n] fp32 on the gradients' device)."""
+def krum_weights(gradients, f: int, m: int | None = None, pre: str | None = None) -> torch.Tensor:
+    """Selection weights of Multi-Krum ([n] fp32 on the gradients' device); ``pre="nnm"``: the row
+    weights of Krum applied after nearest-neighbour mixing (:func:`nnm_weights`)."""
     rows = prepare(gradients)
+    if pre is not None:
+        return _nnm_w(rows, f, "krum", _pre=pre, m=m)
     m = rows.n - f - 2 if m is None else m
     return _krum_weights(rows, f, m)
 
@@ -352,9 +357,12 @@ def _combine_rows(rows: Rows, w: torch.Tensor) -> torch.Tensor:
     return _finish(C.cpu_combine(rows.obj, w), rows)
 
 
-def geomed_weights(gradients, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
+def geomed_weights(gradients, iters: int = 32, nu: float = 1e-6, pre: str | None = None, f: int = 0) -> torch.Tensor:
     """Weights of the geometric median ([n] fp32 on the gradients' device): ``iters`` rounds of
-    smoothed Weiszfeld (RFA) iterated on the pairwise distances alone."""
+    smoothed Weiszfeld (RFA) iterated on the pairwise distances alone. ``pre="nnm"``: the row weights
+    of the geometric median of the rows mixed over their ``n - f`` nearest (:func:`nnm_weights`)."""
+    if pre is not None:
+        return _nnm_w(prepare(gradients), f, "geomed", _pre=pre, iters=iters, nu=nu)
     return _geomed_w(prepare(gradients), iters, nu)
 
 
@@ -379,6 +387,173 @@ def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> tor
     enters the registry's check): Σ_i a_i g_i with the weights of :func:`geomed_weights`."""
     rows = prepare(gradients)
     return _combine_rows(rows, _geomed_w(rows, iters, nu))
+
+
+# Nearest-neighbour mixing (NNM; docs/GAR_SEMANTICS.md): every row is replaced by the mean of its
+# n - f nearest rows, itself included, before the rule runs. Mixing is linear: the mixed rows' distances
+# follow from the Gram, the rule's weights fold back onto the original rows, and the combine kernels
+# consume those: no pass over the d-length rows, no [n, d] buffer of mixed gradients.
+
+NNM_RULES = ("krum", "geomed", "average")
+
+
+def _nnm_args(n: int, f: int, rule: str, pre: str = "nnm", m: int | None = None, iters: int = 32,
+              nu: float = 1e-6) -> tuple:
+    if pre != "nnm":
+        raise ValueError(f"unknown pre-aggregation {pre!r}; available: 'nnm'")
+    if rule not in NNM_RULES:
+        raise ValueError(f"nnm: unsupported rule {rule!r}; available: {NNM_RULES}")
+    if not 0 <= f < n:
+        raise ValueError(f"nnm: expected 0 <= f < n, got f = {f}, n = {n}")
+    if rule == "krum":
+        m = n - f - 2 if m is None else m
+        if n < 2 * f + 3 or not 1 <= m <= n - f - 2:   # Krum's own requirement, as on every other path
+            raise ValueError(f"nnm-krum: expected n >= 2f + 3 and 1 <= m <= n - f - 2, got n = {n}, f = {f}, m = {m}")
+    return m, int(iters), float(nu)
+
+
+def nnm_select(C, ws: Workspace, g: torch.Tensor, n: int, f: int, rule: str, m: int | None = None, iters: int = 32,
+               nu: float = 1e-6) -> torch.Tensor:
+    """Row weights [n] of ``rule`` after the mixing, from a device Gram ``g`` (pitch gram_padded(n),
+    n <= MAX_ROWS): k_nnm_mix -> the rule's own selection on the pseudo-Gram -> k_nnm_unmix. Every
+    buffer comes from ``ws`` (capture-safe)."""
+    np_ = C.gram_padded(n)
+    H = ws.get("nnm_H", np_ * np_)
+    masks = ws.get("nnm_masks", 2 * n, torch.int64)
+    C.gpu_nnm_mix(g, n, f, H, masks)
+    if rule == "krum":
+        a = ws.get("weights", n)
+        C.gpu_krum_select(H, n, f, m, a, ws.get("order", n, torch.int32), ws.get("scores", n))
+    elif rule == "geomed":
+        a = ws.get("weights", n)
+        C.gpu_geomed_select(H, n, iters, nu, a, ws.get("geomed_dists", n))
+    else:
+        a = ws.tensors.get("avg_w")
+        if a is None:
+            a = torch.full((n,), 1.0 / n, dtype=torch.float32, device=g.device)
+            ws.tensors["avg_w"] = a
+    w = ws.get("nnm_w", n)
+    C.gpu_nnm_unmix(a, masks, n, f, w)
+    return w
+
+
+def nnm_from_gram(g: torch.Tensor, f: int) -> tuple:
+    """(H, S) from a Gram matrix, vectorised in fp64 on g's device (any n, no host round trip): the
+    fp32 pseudo-Gram H of the mixed rows (H_ii = 0, H_ij = -D'_ij / 2, so that distances_from_gram(H)
+    = D') and the membership matrix S [n, n] (bool, S_ij: j ∈ S_i). reference.nnm_distances with
+    matrix products for the sums; equal sets give an exact zero."""
+    n = g.shape[0]
+    c = n - f
+    D = distances_from_gram(g).double()
+    key = D.clone()
+    key.fill_diagonal_(-1.0)   # row i itself first, then (distance, index)
+    near = torch.sort(key, dim=1, stable=True).indices[:, :c]
+    S = torch.zeros((n, n), dtype=torch.bool, device=g.device)
+    S.scatter_(1, near, torch.ones_like(near, dtype=torch.bool))
+    Sd = S.double()
+    D.fill_diagonal_(0.0)
+    fin = torch.isfinite(D)
+    M = Sd @ torch.where(fin, D, torch.zeros_like(D)) @ Sd.T / float(c * c)
+    M = torch.triu(M) + torch.triu(M, 1).T
+    bad = (Sd @ (~fin).double() @ Sd.T) > 0    # an infinite pair inside S_i x S_j
+    taint = torch.diagonal(bad)
+    dm = torch.diagonal(M)
+    Dm = (M - 0.5 * dm[:, None] - 0.5 * dm[None, :]).clamp(min=0)
+    Dm = torch.where((Sd @ Sd.T) == c, torch.zeros_like(Dm), Dm)
+    Dm = torch.where(bad | bad.T | taint[:, None] | taint[None, :], torch.full_like(Dm, math.inf), Dm)
+    H = (-0.5 * Dm).float()
+    H.fill_diagonal_(0.0)
+    return H, S
+
+
+def _nnm_fold(S: torch.Tensor, a: torch.Tensor, c: int) -> torch.Tensor:
+    """w_j = (1/c) Σ_{i : j∈S_i} a_i / Σ_i a_i in fp64 (zero a_i add nothing), as fp32."""
+    a = a.to(S.device, torch.float64)
+    acc = torch.where(S, a[:, None], torch.zeros((), dtype=torch.float64, device=S.device)).sum(0)
+    return (acc / a.sum().clamp(min=torch.finfo(torch.float64).tiny) / c).float()
+
+
+def _nnm_w(rows: Rows, f: int, rule: str, _pre: str = "nnm", **kw) -> torch.Tensor:
+    n = rows.n
+    m, iters, nu = _nnm_args(n, f, rule, _pre, **kw)
+    if n > MAX_ROWS:
+        H, S = nnm_from_gram(_large_gram(rows), f)
+        if rule == "krum":
+            a = large_select(H, f, m) if H.is_cuda else krum_weights_from_gram(H, f, m)
+        elif rule == "geomed":
+            a = geomed_weights_from_gram(H, iters, nu)
+        else:
+            a = torch.full((n,), 1.0 / n, dtype=torch.float32, device=H.device)
+        return _nnm_fold(S, a, n - f)
+    C = _C_for(rows)
+    if rows.device.type == "cuda":
+        ws = workspace(rows)
+        return nnm_select(C, ws, _gram_into(C, rows, ws), n, f, rule, m, iters, nu)
+    D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
+    return nnm_weights_from_distances(C, D, f, rule, m, iters, nu)
+
+
+def nnm_weights_from_distances(C, D: torch.Tensor, f: int, rule: str, m: int | None = None, iters: int = 32,
+                               nu: float = 1e-6) -> torch.Tensor:
+    """Row weights [n] (fp32, CPU) of ``rule`` after the mixing, from squared distances: the C++ path
+    (n <= MAX_ROWS: the sets are two mask words), else the oracle."""
+    n = D.shape[0]
+    if C is None or n > MAX_ROWS:
+        return ref.nnm_weights(D, f, rule, m=m, iters=iters, nu=nu)
+    Dm, masks = C.cpu_nnm_mix(D, f)
+    if rule == "krum":
+        a = C.cpu_krum_weights(Dm, f, m)[0]
+    elif rule == "geomed":
+        a = C.cpu_geomed_weights(Dm, iters, nu)
+    else:
+        a = torch.full((n,), 1.0 / n, dtype=torch.float32)
+    return C.cpu_nnm_unmix(a, masks, n - f)
+
+
+def nnm_mix(gradients, f: int) -> tuple:
+    """The mixing alone: ``(H, masks)`` on the GPU for n <= MAX_ROWS (the pseudo-Gram [np, np] the
+    selection kernels take, and the sets as [n, 2] int64 mask words), ``(D', masks)`` on the CPU
+    (fp64 distances of the mixed rows), ``(H, S)`` of :func:`nnm_from_gram` for n > MAX_ROWS.
+    Any 0 <= f < n."""
+    rows = prepare(gradients)
+    if not 0 <= f < rows.n:
+        raise ValueError(f"nnm: expected 0 <= f < n, got f = {f}, n = {rows.n}")
+    if rows.n > MAX_ROWS:
+        return nnm_from_gram(_large_gram(rows), f)
+    C = _C_for(rows)
+    if rows.device.type == "cuda":
+        ws = workspace(rows)
+        g = _gram_into(C, rows, ws)
+        np_ = C.gram_padded(rows.n)
+        H = torch.zeros(np_ * np_, dtype=torch.float32, device=rows.device)
+        masks = torch.empty((rows.n, 2), dtype=torch.int64, device=rows.device)
+        C.gpu_nnm_mix(g, rows.n, f, H, masks)
+        return H.view(np_, np_), masks
+    if C is None:
+        sets, Dm = ref.nnm_distances(ref.pairwise_sqdist(rows.stacked()), f)
+        return Dm, masks_from_sets(sets)
+    return C.cpu_nnm_mix(C.cpu_pairwise(rows.obj), f)
+
+
+def masks_from_sets(sets) -> torch.Tensor:
+    """[n, 2] int64 mask words of neighbour sets given as index lists (n <= 128)."""
+    out = []
+    for s in sets:
+        v = sum(1 << j for j in s)
+        out.append([((v >> (64 * k)) & ((1 << 64) - 1)) for k in range(2)])
+    return torch.tensor([[x - (1 << 64) if x >= (1 << 63) else x for x in r] for r in out], dtype=torch.int64)
+
+
+def nnm_weights(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
+    """Weights over the ORIGINAL rows ([n] fp32 on the gradients' device) of ``rule`` (krum: ``m``;
+    geomed: ``iters``, ``nu``; average) applied to the rows mixed over their n - f nearest."""
+    return _nnm_w(prepare(gradients), f, rule, **kw)
+
+
+def nnm(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
+    """``rule`` after nearest-neighbour mixing: Σ_j w_j g_j with the weights of :func:`nnm_weights`."""
+    rows = prepare(gradients)
+    return _combine_rows(rows, _nnm_w(rows, f, rule, **kw))
 
 
 def bulyan_weights(gradients, f: int, m: int | None = None) -> torch.Tensor:
@@ -728,6 +903,9 @@ RULES = {
     "brute": brute,
     "aksel": aksel,
     "geomed": geomed,
+    "nnm-krum": lambda gradients, f, m=None, **_: nnm(gradients, f, "krum", m=m),
+    "nnm-geomed": lambda gradients, f=0, iters=32, nu=1e-6, **_: nnm(gradients, f, "geomed", iters=iters, nu=nu),
+    "nnm-average": lambda gradients, f=0, **_: nnm(gradients, f, "average"),
     "condense": condense,
     "trimmed-mean": trimmed_mean,
     "averaged-median": averaged_median,

@@ -129,6 +129,104 @@ def geomed(G, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
     return combine(G, geomed_weights(pairwise_sqdist(G), iters, nu))
 
 
+# Nearest-neighbour mixing (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing"): every gradient is
+# replaced by the mean of its c = n - f nearest gradients, itself included, before a rule runs.
+# Mixing is linear, so everything below works on the squared distances alone.
+
+
+def nnm_sets(D: torch.Tensor, f: int) -> list[list[int]]:
+    """S_i (ascending indices): the first c = n - f indices j by the key (j != i, D_ij, j)."""
+    n = D.shape[0]
+    if not 0 <= f < n:
+        raise ValueError(f"nnm: expected 0 <= f < n, got f = {f}, n = {n}")
+    c = n - f
+    sets = []
+    for i in range(n):
+        row = D[i].tolist()
+        order = sorted(range(n), key=lambda j: (j != i, _key(float(row[j])) if j != i else 0.0, j))
+        sets.append(sorted(order[:c]))
+    return sets
+
+
+def nnm_distances(D: torch.Tensor, f: int):
+    """(sets, D'): the neighbour sets and the squared distances [n, n] (fp64, +inf diagonal) of the
+    mixed rows y_i = (1/c) Σ_{j∈S_i} x_j, from D alone: with D⁰ = D with a zero diagonal and
+    M_ij = (1/c²) Σ_{k∈S_i} Σ_{l∈S_j} D⁰_kl, ||y_i - y_j||² = M_ij - ½M_ii - ½M_jj (clamped at 0).
+    +inf when i or j is tainted (two members of its set at distance +inf) or a cross pair is +inf.
+    Sums run over the set members in ascending index, the inner sum (over l) first."""
+    D = D.detach().to(device="cpu", dtype=torch.float64)
+    n = D.shape[0]
+    sets = nnm_sets(D, f)
+    c = n - f
+    d0 = [[0.0 if k == l else _key(float(v)) for l, v in enumerate(row)] for k, row in enumerate(D.tolist())]
+    # R[j][k] = Σ_{l∈S_j} D⁰_kl ; distances are >= 0 or +inf, so a sum is +inf iff a term is
+    R = []
+    for j in range(n):
+        col = []
+        for k in range(n):
+            acc, row = 0.0, d0[k]
+            for l in sets[j]:
+                acc += row[l]
+            col.append(acc)
+        R.append(col)
+
+    def m_of(i, j):
+        acc, col = 0.0, R[j]
+        for k in sets[i]:
+            acc += col[k]
+        return acc / (c * c)
+
+    diag = [m_of(i, i) for i in range(n)]
+    out = torch.full((n, n), math.inf, dtype=torch.float64)
+    for i in range(n):
+        for j in range(i + 1, n):
+            mij = m_of(i, j)
+            if math.isinf(mij) or math.isinf(diag[i]) or math.isinf(diag[j]):
+                v = math.inf
+            else:
+                v = max(mij - 0.5 * diag[i] - 0.5 * diag[j], 0.0)
+            out[i, j] = out[j, i] = v
+    return sets, out
+
+
+def nnm_row_weights(sets, a) -> torch.Tensor:
+    """Fold weights a over the mixed rows back into weights over the original rows (fp32):
+    w_j = (1/c) Σ_{i : j∈S_i} a_i / Σ_i a_i, i ascending in fp64, terms with a_i == 0 skipped. The
+    division by Σ_i a_i (1 up to the rounding of a) makes equal sets give exactly 1/n."""
+    n = len(sets)
+    c = len(sets[0])
+    acc, tot = [0.0] * n, 0.0
+    for i in range(n):
+        ai = float(a[i])
+        if ai == 0.0:
+            continue
+        tot += ai
+        for j in sets[i]:
+            acc[j] += ai
+    if tot == 0.0:
+        return torch.zeros(n, dtype=torch.float32)
+    return torch.tensor([v / tot / c for v in acc], dtype=torch.float64).float()
+
+
+def nnm_weights(D: torch.Tensor, f: int, rule: str = "krum", **kw) -> torch.Tensor:
+    """Row weights [n] (fp32) of ``rule`` (krum / geomed / average) applied after the mixing."""
+    sets, Dm = nnm_distances(D, f)
+    n = D.shape[0]
+    if rule == "krum":
+        a = krum_weights(Dm, f, kw.get("m"))
+    elif rule == "geomed":
+        a = geomed_weights(Dm, kw.get("iters", 32), kw.get("nu", 1e-6))
+    elif rule == "average":
+        a = torch.full((n,), 1.0 / n, dtype=torch.float64)
+    else:
+        raise ValueError(f"nnm: unsupported rule {rule!r} (krum, geomed, average)")
+    return nnm_row_weights(sets, a)
+
+
+def nnm(G, f: int, rule: str = "krum", **kw) -> torch.Tensor:
+    return combine(G, nnm_weights(pairwise_sqdist(G), f, rule, **kw).double())
+
+
 def bulyan_weights(D: torch.Tensor, f: int, m: int | None = None) -> torch.Tensor:
     n = D.shape[0]
     m = n - f - 2 if m is None else m

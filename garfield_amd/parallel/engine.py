@@ -100,6 +100,12 @@ class EngineConfig:
     f: int = 2
     m: int | None = None
     gar_kwargs: dict = field(default_factory=dict)
+    # "nnm": nearest-neighbour mixing before the rule (every gradient replaced by the mean of its
+    # n - f nearest, itself included; docs/GAR_SEMANTICS.md), folded into the rule's row weights, for
+    # gar in {krum, geomed, average}: the flat step (GPU, CPU, n > 128), explicit row lists and the
+    # sharded flat selection. Not yet supported (ValueError at construction): any other rule,
+    # layerwise=True, and the sharded path with n > 128 rows on the GPU. None: exactly today's paths.
+    pre_aggregation: str | None = None
     workers_per_rank: int = 8
     lr: float = 0.1
     momentum: float = 0.9
@@ -193,6 +199,7 @@ class RobustDataParallel:
         self.ctx = ctx
         self.cfg = cfg
         self.device = ctx.device
+        self._check_pre_aggregation()
         self.model = model.to(self.device)
         self._grouping = self._want_grouping(self.model)
         if (cfg.channels_last and self.device.type == "cuda") or self._grouping:
@@ -408,10 +415,35 @@ class RobustDataParallel:
         """Global slot id (row of the [n, d] GAR input) of local worker j."""
         return j * self.world + self.rank
 
+    def _check_pre_aggregation(self) -> None:
+        cfg = self.cfg
+        if cfg.pre_aggregation is None:
+            return
+        if cfg.pre_aggregation != "nnm":
+            raise ValueError(f"unknown pre_aggregation {cfg.pre_aggregation!r}; available: 'nnm'")
+        if cfg.gar not in gar.NNM_RULES:
+            raise ValueError(f"pre_aggregation='nnm' is not yet supported with gar={cfg.gar!r}; "
+                             f"available: {gar.NNM_RULES}")
+        if cfg.layerwise:
+            raise ValueError("pre_aggregation='nnm' is not yet supported with layerwise=True")
+        if (self.device.type == "cuda" and cfg.workers_per_rank * self.ctx.world_size > gar.MAX_ROWS
+                and self._want_sharded()):
+            raise ValueError(f"pre_aggregation='nnm' is not yet supported by the sharded aggregation of more than "
+                             f"{gar.MAX_ROWS} rows (shard_gar=False runs the unsharded path)")
+
+    def _nnm_kwargs(self, kw: dict) -> dict:
+        """The rule's keyword arguments of gar.nnm_weights."""
+        if self.cfg.gar == "krum":
+            return {"m": self.cfg.m}
+        if self.cfg.gar == "geomed":
+            iters, nu = self._geomed_args(kw)
+            return {"iters": iters, "nu": nu}
+        return {}
+
     def _check_gar(self) -> None:
         from garfield_amd import aggregators
 
-        rule = aggregators.get(self.cfg.gar)
+        rule = aggregators.get(("nnm-" if self.cfg.pre_aggregation else "") + self.cfg.gar)
         kw = dict(self.cfg.gar_kwargs)
         if self.cfg.m is not None:
             kw["m"] = self.cfg.m
@@ -510,7 +542,7 @@ class RobustDataParallel:
                 gkw["m"] = cfg.m
             if rule == "condense":
                 gkw.setdefault("seed", cfg.seed + self.step_count)
-            if rule == "geomed":   # continuous weights: kept for last_weights, then the rule's own combine
+            if rule == "geomed" or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
                 self.last_weights = w = self._weights(rule, kw, self.G.float())
                 g = gar.combine(self.G.float(), w).float()
             else:
@@ -634,6 +666,8 @@ class RobustDataParallel:
     def _weights(self, rule: str, kw: dict, G=None) -> torch.Tensor:
         f = self.cfg.f
         G = self.G if G is None else G
+        if self.cfg.pre_aggregation:   # the rule on the mixed rows, folded back into row weights
+            return gar.nnm_weights(G, f, rule, **self._nnm_kwargs(kw))
         if rule == "average":
             w = getattr(self, "_avg_w", None)
             if w is None:
@@ -699,7 +733,9 @@ class RobustDataParallel:
         if self.device.type == "cuda":
             C = self._C
             if cfg.gar in WEIGHTED_RULES:
-                if cfg.gar == "krum":
+                if cfg.pre_aggregation:
+                    w = gar.nnm_weights(rows, cfg.f, cfg.gar, **self._nnm_kwargs(cfg.gar_kwargs))
+                elif cfg.gar == "krum":
                     w = gar.krum_weights(rows, cfg.f, cfg.m)
                 elif cfg.gar == "brute":
                     w = gar.brute_weights(rows, cfg.f)
@@ -725,7 +761,12 @@ class RobustDataParallel:
         else:
             # as a [rows, d] fp32 matrix: the aggregate keeps fp32 (a list of 16-bit rows
             # would round it to the rows' dtype), as the synchronous step's
-            g = gar.aggregate(cfg.gar, torch.stack([r.float() for r in rows]), **self._rule_kwargs()).float()
+            X = torch.stack([r.float() for r in rows])
+            if cfg.pre_aggregation:
+                self.last_weights = w = gar.nnm_weights(X, cfg.f, cfg.gar, **self._nnm_kwargs(cfg.gar_kwargs))
+                g = gar.combine(X, w).float()
+            else:
+                g = gar.aggregate(cfg.gar, X, **self._rule_kwargs()).float()
             self._sgd_cpu(g, first)
 
     def _sgd_cpu(self, g: torch.Tensor, first: bool) -> None:

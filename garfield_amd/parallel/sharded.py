@@ -524,7 +524,7 @@ class ShardedAggregator:
         n = self.n
         args = (cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
         modes = gar._MODE
-        if rule in DISTANCE_RULES or rule == "aksel":
+        if rule in DISTANCE_RULES or rule == "aksel" or cfg.pre_aggregation:
             total = None
             slabs = []
             for b in self.buckets:   # partial statistics as the buckets land
@@ -683,6 +683,8 @@ class ShardedAggregator:
         n = self.n
         ws = self._ws_any()
         m = cfg.m if cfg.m is not None else n - f - 2
+        if cfg.pre_aggregation:   # after the partial Grams are summed over ranks: the same w on every rank
+            return gar.nnm_select(C, ws, gram_total, n, f, rule, m, *self.e._geomed_args(cfg.gar_kwargs))
         if rule == "krum":
             w = ws.get("weights", n)
             order = ws.get("order", n, torch.int32)
@@ -914,7 +916,7 @@ class ShardedAggregator:
         e = self.e
         rule, f, kw = cfg.gar, cfg.f, dict(cfg.gar_kwargs)
         n = self.n
-        if rule in DISTANCE_RULES or rule == "aksel":
+        if rule in DISTANCE_RULES or rule == "aksel" or cfg.pre_aggregation:
             C = _native.require_for(X.device)
             if rule == "aksel":
                 med = gar.aggregate("median", X)
@@ -929,6 +931,10 @@ class ShardedAggregator:
                 return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
             D = self._sum_over_ranks(gar.pairwise_distances(X))
             m = cfg.m if cfg.m is not None else n - f - 2
+            if cfg.pre_aggregation:   # the mix runs on the summed distances: the same w on every rank
+                w = gar.nnm_weights_from_distances(C, D, f, rule, m, *e._geomed_args(kw))
+                e.last_weights = w
+                return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
             if rule == "bulyan":
                 t = n - 2 * f - 2
                 e.last_weights = None

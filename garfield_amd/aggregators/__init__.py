@@ -14,8 +14,9 @@ Reference: ``pytorch_impl/libs/aggregators/__init__.py:15-97``.
   implementation (gfx950 HIP on GPU tensors, C++ thread pool on CPU tensors).
 * New rules (absent from the PyTorch reference): ``trimmed-mean``, and the TF-only
   ``average-nan`` and ``averaged-median``; ``geomed`` (geometric median, absent from both
-  references); ``nnm-krum`` / ``nnm-geomed`` / ``nnm-average`` (nearest-neighbour mixing before the
-  rule, absent from both references).
+  references); ``cclip`` (centered clipping, absent from both references); ``nnm-krum`` /
+  ``nnm-geomed`` / ``nnm-cclip`` / ``nnm-average`` (nearest-neighbour mixing before the rule, absent from
+  both references).
 """
 from __future__ import annotations
 
@@ -57,7 +58,7 @@ def register(name, unchecked, check, upper_bound=None, influence=None):
 
 
 _MODULES = ("average", "median", "krum", "bulyan", "brute", "aksel", "condense", "trimmed_mean",
-            "average_nan", "averaged_median", "geomed", "nnm")
+            "average_nan", "averaged_median", "geomed", "cclip", "nnm")
 for _m in _MODULES:
     importlib.import_module(f"garfield_amd.aggregators.{_m}")
 

@@ -142,6 +142,19 @@ class GeoMedGAR(_GAR):
         return {"iters": int(self.args["iters"]), "nu": float(self.args["nu"])}
 
 
+class CClipGAR(_GAR):
+    """Centered clipping (new, absent from the reference); ``tau:<float>`` (0: from the data), ``iters:<int>``,
+    ``start:mean|krum`` and ``m:<int>`` (the Krum start's selection size) optional."""
+    rule_name = "cclip"
+    defaults = {"tau": 0.0, "iters": 3, "start": "mean", "m": 0}
+
+    def kwargs(self):
+        kw = {"tau": float(self.args["tau"]) or None, "iters": int(self.args["iters"]), "start": str(self.args["start"])}
+        if self.args["m"]:
+            kw["m"] = int(self.args["m"])
+        return kw
+
+
 class NNMKrumGAR(KrumGAR):
     """Multi-Krum after nearest-neighbour mixing over the n - f nearest (new, absent from the reference)."""
     rule_name = "nnm-krum"
@@ -150,6 +163,11 @@ class NNMKrumGAR(KrumGAR):
 class NNMGeoMedGAR(GeoMedGAR):
     """Geometric median after nearest-neighbour mixing (new, absent from the reference)."""
     rule_name = "nnm-geomed"
+
+
+class NNMCClipGAR(CClipGAR):
+    """Centered clipping after nearest-neighbour mixing (new, absent from the reference)."""
+    rule_name = "nnm-cclip"
 
 
 class NNMAverageGAR(_GAR):
@@ -167,5 +185,5 @@ for _name, _cls in (("average", AverageGAR), ("average-nan", AverageNaNGAR), ("m
                     ("krum-tf", KrumGAR), ("bulyan", BulyanGAR), ("bulyan-py", BulyanGAR),
                     ("condense", CondenseGAR), ("trimmed-mean", TrimmedMeanGAR),
                     ("geomed", GeoMedGAR), ("nnm-krum", NNMKrumGAR), ("nnm-geomed", NNMGeoMedGAR),
-                    ("nnm-average", NNMAverageGAR)):
+                    ("nnm-average", NNMAverageGAR), ("cclip", CClipGAR), ("nnm-cclip", NNMCClipGAR)):
     register(_name, _cls)

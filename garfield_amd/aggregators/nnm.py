@@ -1,11 +1,12 @@
 """Nearest-neighbour mixing (NNM; Allouah et al., "Fixing by Mixing", AISTATS 2023) in front of a
 rule (new, absent from the reference): every gradient is replaced by the mean of its ``n - f``
-nearest gradients, itself included, then Krum, the geometric median or the average runs on the
-mixed gradients. The mixing is folded into the rule's weights (``docs/GAR_SEMANTICS.md``
+nearest gradients, itself included, then Krum, the geometric median, centered clipping or the average
+runs on the mixed gradients. The mixing is folded into the rule's weights (``docs/GAR_SEMANTICS.md``
 "Nearest-neighbour mixing"): the aggregate is Σ_j w_j g_j over the ORIGINAL gradients."""
 from garfield_amd.aggregators import register
 from garfield_amd.aggregators._common import n_of
 from garfield_amd.aggregators.average import check as _average_check
+from garfield_amd.aggregators.cclip import check as _cclip_check
 from garfield_amd.aggregators.geomed import check as _geomed_check
 from garfield_amd.aggregators.krum import check as _krum_check
 from garfield_amd.ops import gar
@@ -18,8 +19,10 @@ def _check_mix(gradients, f):
     return None
 
 
-def _rule_kwargs(rule, m=None, iters=32, nu=1e-6, **kwargs):
-    return {"krum": {"m": m}, "geomed": {"iters": iters, "nu": nu}, "average": {}}[rule]
+def _rule_kwargs(rule, m=None, iters=None, nu=1e-6, tau=None, start=None, **kwargs):
+    if rule == "cclip":
+        return {"m": m, "iters": 3 if iters is None else iters, "tau": tau, "start": "mean" if start is None else start}
+    return {"krum": {"m": m}, "geomed": {"iters": 32 if iters is None else iters, "nu": nu}, "average": {}}[rule]
 
 
 def _make(rule, own_check):
@@ -32,6 +35,8 @@ def _make(rule, own_check):
         msg = own_check(gradients=gradients, f=f, **kwargs)
         if msg:
             return msg
+        if rule == "cclip" and (kwargs.get("center") is not None or not isinstance(kwargs.get("start") or "", str)):
+            return "Invalid start, expected 'mean' or 'krum' (computed on the mixed gradients) and no center"
         return _check_mix(gradients, f)
 
     def influence(honests, attacks, f=0, **kwargs):
@@ -45,4 +50,5 @@ def _make(rule, own_check):
 
 _make("krum", _krum_check)
 _make("geomed", _geomed_check)
+_make("cclip", _cclip_check)
 _make("average", _average_check)

@@ -44,7 +44,7 @@ def add_common(p: argparse.ArgumentParser, ps: bool = True) -> argparse.Argument
     p.add_argument("--num_iter", type=int, default=5000)
     p.add_argument("--gar", type=str, default="average")
     p.add_argument("--pre_aggregation", type=str, default=None, choices=["nnm"],
-                   help="nnm: nearest-neighbour mixing before --gar (krum, geomed, average): every gradient is "
+                   help="nnm: nearest-neighbour mixing before --gar (krum, geomed, cclip, average): every gradient is "
                         "replaced by the mean of its n - f nearest, for heterogeneous (--non_iid) data")
     p.add_argument("--acc_freq", type=int, default=100, help="Accuracy evaluation period (iterations).")
     p.add_argument("--bench", type=str2bool, default=False, help="Print per-step timing and bandwidth.")

@@ -23,12 +23,15 @@ import torch
 from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
-         "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average"]
+         "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average", "cclip", "cclip-krum", "nnm-cclip"]
+# "cclip-krum": centered clipping from the Multi-Krum start (start="krum"), Krum's f
 
 
 def default_f(rule: str, n: int) -> int | None:
     if rule.startswith("nnm-"):   # the f of the plain rule (average: as geomed), so the pair is comparable
         rule = "geomed" if rule == "nnm-average" else rule[4:]
+    if rule == "cclip-krum":
+        rule = "krum"
     if rule in ("average", "average-nan", "median"):
         return None
     if rule == "bulyan":
@@ -47,6 +50,8 @@ def bench_rule(rule, G, f, iters, warmup):
     kw = {} if f is None else {"f": f}
     if rule == "averaged-median":
         kw = {"f": f or 0}
+    if rule == "cclip-krum":
+        rule, kw = "cclip", dict(kw, start="krum")
     for _ in range(warmup):
         gar.aggregate(rule, G, **kw)
     dev = G.device if isinstance(G, torch.Tensor) else G[0].device
@@ -84,7 +89,7 @@ def main(argv=None):
             inp = [G[i].clone() for i in range(n)] if a.list_input else G
             for rule in a.rules:
                 f = default_f(rule, n)
-                if rule in ("krum", "nnm-krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense") and f is None:
+                if rule in ("krum", "nnm-krum", "cclip-krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense") and f is None:
                     continue
                 if rule == "brute" and n > 20:
                     continue

@@ -71,7 +71,7 @@ def parse(argv=None):
     p.add_argument("--num_iter", type=int, default=0, help="stop after this many iterations (0: epochs)")
     p.add_argument("--aggregator", default="vanilla", help="GAR name; vanilla = average (reference default)")
     p.add_argument("--pre_aggregation", default=None, choices=["nnm"],
-                   help="nnm: nearest-neighbour mixing before --aggregator (krum, geomed, average)")
+                   help="nnm: nearest-neighbour mixing before --aggregator (krum, geomed, cclip, average)")
     p.add_argument("--mar", default="median")
     p.add_argument("--attack", default="", help="attack of the fw Byzantine worker slots")
     p.add_argument("--ps_attack", default="", help="attack of the fps Byzantine servers")

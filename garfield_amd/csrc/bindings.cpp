@@ -1983,6 +1983,33 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      py::arg("batch") = 1,
      "Geometric-median weights (smoothed Weiszfeld on the Gram's distances) on device; dists = the iterate's "
      "distance to every row; batch > 1: gram [batch, np, np] -> weights / dists [batch, n]");
+  m.def("gpu_cclip_select", [](const at::Tensor& gram, int n, int nw, const c10::optional<at::Tensor>& a0, double tau,
+                               int f, int iters, const at::Tensor& w, const at::Tensor& dists, int batch) {
+    c10::hip::HIPGuard guard(gram.device().index());
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_cclip_select: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(nw >= 1 && nw <= n, "gpu_cclip_select: 1 <= nw <= n");
+    TORCH_CHECK(iters >= 1 && f >= 0, "gpu_cclip_select: iters >= 1 and f >= 0");
+    TORCH_CHECK(tau == tau, "gpu_cclip_select: tau must not be NaN");
+    TORCH_CHECK(batch >= 1, "batch must be >= 1");
+    TORCH_CHECK(gram.is_cuda() && w.is_cuda() && dists.is_cuda(), "gpu_cclip_select: GPU tensors expected");
+    const int np = garfield::gpu::gram_padded(n);
+    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && w.numel() >= static_cast<int64_t>(batch) * n &&
+                    dists.numel() >= static_cast<int64_t>(batch) * n,
+                "gpu_cclip_select: buffers too small for the batch");
+    const float* start = nullptr;
+    if (a0.has_value()) {
+      TORCH_CHECK(a0->is_cuda() && a0->scalar_type() == at::kFloat && a0->is_contiguous() &&
+                      a0->numel() >= static_cast<int64_t>(batch) * n,
+                  "gpu_cclip_select: a0 must be a contiguous fp32 GPU tensor of [batch, n]");
+      start = fptr(*a0);
+    }
+    garfield::gpu::cclip_select(fptr(gram), np, n, nw, start, tau, f, iters, fptr(w), fptr(dists),
+                                stream_of(gram.device()), batch);
+  }, py::arg("gram"), py::arg("n"), py::arg("nw"), py::arg("a0"), py::arg("tau"), py::arg("f"), py::arg("iters"),
+     py::arg("weights"), py::arg("dists"), py::arg("batch") = 1,
+     "Centered-clipping weights (iters clipping rounds on the Gram's distances) on device; rows nw..n-1 are basis-only; "
+     "a0 = the start weights (None: uniform on the workers; may be the weights buffer); tau <= 0: the radius from the "
+     "data; dists = the centre's distance to every valid worker; batch > 1: gram [batch, np, np] -> weights / dists [batch, n]");
   m.def("gpu_nnm_mix", [](const at::Tensor& gram, int n, int f, const at::Tensor& H, const at::Tensor& masks,
                           int batch) {
     c10::hip::HIPGuard guard(gram.device().index());
@@ -2659,6 +2686,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return weights_tensor(garfield::cpu::geomed_weights(dist_from(D), n, iters, nu), {n});
   }, py::arg("D"), py::arg("iters") = 32, py::arg("nu") = 1e-6,
      "Geometric-median (smoothed Weiszfeld) weights from squared distances (fp32 [n])");
+  m.def("cpu_cclip_weights", [](const at::Tensor& D, int nw, const c10::optional<at::Tensor>& a0, double tau, int f,
+                                int iters) {
+    TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_cclip_weights: D must be [n, n]");
+    const int64_t n = D.size(0);
+    TORCH_CHECK(nw >= 1 && nw <= n, "cpu_cclip_weights: 1 <= nw <= n");
+    TORCH_CHECK(iters >= 1 && f >= 0 && tau == tau, "cpu_cclip_weights: iters >= 1, f >= 0 and tau not NaN");
+    std::vector<double> start;
+    if (a0.has_value()) {
+      TORCH_CHECK(a0->numel() == n, "cpu_cclip_weights: a0 must have n entries");
+      start = dist_from(*a0);
+    }
+    return weights_tensor(garfield::cpu::cclip_weights(dist_from(D), n, nw, start, tau, f, iters), {n});
+  }, py::arg("D"), py::arg("nw"), py::arg("a0"), py::arg("tau"), py::arg("f"), py::arg("iters") = 3,
+     "Centered-clipping weights from squared distances (fp32 [n]); a0 None: uniform on the workers; tau <= 0: from the data");
   m.def("cpu_nnm_mix", [](const at::Tensor& D, int f) {
     TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_nnm_mix: D must be [n, n]");
     const int64_t n = D.size(0);

@@ -146,6 +146,73 @@ std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t
   return w;
 }
 
+// Centered clipping on the distance matrix alone (docs/GAR_SEMANTICS.md "Centered clipping"):
+// exactly `iters` rounds, every sum in index order.
+std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t nw, const std::vector<double>& a0,
+                                 double tau, size_t f, size_t iters) {
+  std::vector<char> valid(n, 0);
+  size_t nv = 0;   // |V|: the valid workers
+  for (size_t i = 0; i < n; ++i) {
+    for (size_t j = 0; j < n; ++j)
+      if (j != i && std::isfinite(D[i * n + j])) valid[i] = 1;
+    if (i < nw) nv += valid[i];
+  }
+  std::vector<float> w(n, 0.f);
+  if (nv == 0) {
+    for (size_t i = 0; i < nw; ++i) w[i] = static_cast<float>(1.0 / static_cast<double>(nw));
+    return w;
+  }
+  auto dist = [&](size_t i, size_t j) {
+    const double v = D[i * n + j];
+    return (i != j && std::isfinite(v)) ? v : 0.0;
+  };
+  const double nvd = static_cast<double>(nv);
+  std::vector<double> a(n, 0.0), s(n, 0.0), r(n, 0.0), lam(n, 0.0);
+  double tot = 0.0;
+  if (!a0.empty())
+    for (size_t i = 0; i < n; ++i)
+      if (valid[i]) tot += (a[i] = a0[i]);
+  if (!a0.empty() && std::isfinite(tot) && tot > 0.0) {
+    for (size_t i = 0; i < n; ++i) a[i] /= tot;
+  } else {
+    for (size_t i = 0; i < n; ++i) a[i] = (i < nw && valid[i]) ? 1.0 / nvd : 0.0;
+  }
+  const size_t k = nv > f ? nv - f : 1;
+  for (size_t it = 0; it < iters; ++it) {
+    for (size_t i = 0; i < n; ++i) {
+      if (!valid[i]) continue;
+      double acc = 0.0;
+      for (size_t j = 0; j < n; ++j)
+        if (valid[j]) acc += a[j] * dist(i, j);
+      s[i] = acc;
+    }
+    double q = 0.0;
+    for (size_t i = 0; i < n; ++i)
+      if (valid[i]) q += a[i] * s[i];
+    q *= 0.5;
+    for (size_t i = 0; i < nw; ++i)
+      if (valid[i]) r[i] = std::sqrt(std::max(s[i] - q, 0.0));
+    double t = tau;
+    if (!(tau > 0.0)) {   // the k-th smallest r over V: only its value is used
+      std::vector<double> rs;
+      for (size_t i = 0; i < nw; ++i)
+        if (valid[i]) rs.push_back(r[i]);
+      std::nth_element(rs.begin(), rs.begin() + (k - 1), rs.end());
+      t = rs[k - 1];
+    }
+    double Lam = 0.0;
+    for (size_t i = 0; i < nw; ++i) {
+      if (!valid[i]) continue;
+      lam[i] = r[i] <= t ? 1.0 : t / r[i];
+      Lam += lam[i];
+    }
+    const double keep = 1.0 - Lam / nvd;
+    for (size_t i = 0; i < n; ++i) a[i] = a[i] * keep + lam[i] / nvd;
+  }
+  for (size_t i = 0; i < n; ++i) w[i] = static_cast<float>(a[i]);
+  return w;
+}
+
 // Nearest-neighbour mixing (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing"): the oracle's sums in
 // the oracle's order (set members ascending, the inner sum over l first).
 std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, std::vector<uint64_t>* masks) {

@@ -34,6 +34,11 @@ std::vector<float> aksel_weights(const std::vector<double>& dists, size_t n, siz
 // Geometric median (smoothed Weiszfeld, `iters` rounds on D alone): rows without a finite
 // off-diagonal distance get weight 0; none valid -> uniform 1/n.
 std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t iters, double nu);
+// Centered clipping (`iters` rounds on D alone; docs/GAR_SEMANTICS.md): rows 0..nw-1 are the workers,
+// rows nw..n-1 basis-only; a0 (empty: uniform on the workers) the start weights; tau > 0 the radius,
+// tau <= 0 the max(|V| - f, 1)-th smallest distance of the centre to a valid worker, every round.
+std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t nw, const std::vector<double>& a0,
+                                 double tau, size_t f, size_t iters);
 
 // Nearest-neighbour mixing on D alone (0 <= f < n, c = n - f; docs/GAR_SEMANTICS.md). nnm_mix: masks[2n]
 // (row i's set, i and its c - 1 nearest, as two 64-bit words; n <= 128) and the squared distances D' of

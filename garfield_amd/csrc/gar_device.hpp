@@ -180,6 +180,23 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Σ_{i < n} x[i] y[i] (y == nullptr: Σ x[i]) by one wave, n <= 128; identical on every wave
+__device__ __forceinline__ double wave_dot(const double* x, const double* y, int n, int lane) {
+  double acc = 0.0;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int i = lane + 64 * c;
+    if (i < n) acc += y ? x[i] * y[i] : x[i];
+  }
+  return wave_sum_f64(acc);
+}
+
 // Squared distances D (LDS, pitch n + 1) from a Gram matrix (pitch np) by the whole workgroup:
 // non-finite -> +inf, clamped at 0, `diag` on the diagonal. Shared by the one-workgroup selections.
 __device__ __forceinline__ void fill_distances(const float* __restrict__ gram, int np, int n, float* D,

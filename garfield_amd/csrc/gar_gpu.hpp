@@ -34,6 +34,15 @@ void krum_select(const float* gram, int np, int n, int f, int m, float* weights,
 void geomed_select(const float* gram, int np, int n, int iters, double nu, float* weights, float* dists,
                    hipStream_t stream, int batch = 1);
 
+// Centered clipping (gar_cclip.hip): `iters` clipping rounds on the distances of the Gram (n <= kMaxRows).
+// Rows 0..nw-1 are the workers, rows nw..n-1 basis-only (an appended centre). a0[n]: the start weights
+// (nullptr: uniform on the workers; may alias weights). tau > 0: the absolute L2 radius; tau <= 0: from
+// the data, the max(|V| - f, 1)-th smallest distance of the centre to a valid worker, every round.
+// weights[n] = the centre's coefficients, dists[n] = its distance r_i to every valid worker before the
+// last round (+inf elsewhere). batch as krum_select (a0, when given, [batch][n]).
+void cclip_select(const float* gram, int np, int n, int nw, const float* a0, double tau, int f, int iters,
+                  float* weights, float* dists, hipStream_t stream, int batch = 1);
+
 // Nearest-neighbour mixing (gar_nnm.hip), n <= kMaxRows, 0 <= f < n, c = n - f. nnm_mix: from the Gram,
 // masks[n][2] (the set S_i of row i as two 64-bit words: i and its c - 1 nearest) and the pseudo-Gram
 // H [np][np] (H_ii = 0, H_ij = -D'_ij / 2 with D' the squared distances of the mixed rows), on which

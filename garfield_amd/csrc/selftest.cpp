@@ -131,6 +131,38 @@ static void test_nnm() {
   CHECK(w[6] == 0.f && w[5] == 0.f && w[0] == 0.2f);
 }
 
+// Centered clipping on points on a line: one round with a radius above every distance lands on the
+// exact mean of the valid workers from any start (a centre row keeps no weight); a small radius moves
+// the centre by exactly that radius; the non-finite row takes no weight.
+static void test_cclip() {
+  const size_t n = 6, nw = 5;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double pos[n] = {0.0, 0.1, 0.2, 10.0, 0.0 /* non-finite */, 3.0 /* the centre */};
+  std::vector<double> D(n * n, inf);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < n; ++j)
+      if (i != j && i != 4 && j != 4) D[i * n + j] = (pos[i] - pos[j]) * (pos[i] - pos[j]);
+  std::vector<double> at_centre(n, 0.0);
+  at_centre[n - 1] = 1.0;
+  auto w = cpu::cclip_weights(D, n, nw, at_centre, 1e30, 1, 1);
+  for (size_t i = 0; i < 4; ++i) CHECK(w[i] == 0.25f);
+  CHECK(w[4] == 0.f && w[5] == 0.f);
+  // from the centre at 3.0 with radius 0.5: every worker is farther, so the centre moves by
+  // (1/4) (3 x -0.5 + 0.5) = -0.25
+  w = cpu::cclip_weights(D, n, nw, at_centre, 0.5, 1, 1);
+  double v = 0.0, tot = 0.0;
+  for (size_t i = 0; i < n; ++i) {
+    v += static_cast<double>(w[i]) * pos[i];
+    tot += w[i];
+  }
+  CHECK(std::fabs(tot - 1.0) < 1e-6 && std::fabs(v - 2.75) < 1e-5 && w[4] == 0.f);
+  // the data-derived radius with f = 1 from the mean (2.575): the 3rd smallest distance, 2.575
+  w = cpu::cclip_weights(D, n, nw, {}, 0.0, 1, 1);
+  v = 0.0;
+  for (size_t i = 0; i < n; ++i) v += static_cast<double>(w[i]) * pos[i];
+  CHECK(std::fabs(v - (2.575 + 0.25 * (-2.575 - 2.475 - 2.375 + 2.575))) < 1e-5);
+}
+
 static void test_mailbox() {
   mailbox::Mailbox mb(8, 4096, false);
   std::vector<std::thread> writers;
@@ -155,6 +187,7 @@ int main() {
   test_pool();
   test_gars();
   test_nnm();
+  test_cclip();
   test_mailbox();
   if (failures) {
     std::fprintf(stderr, "selftest: %d failure(s)\n", failures);

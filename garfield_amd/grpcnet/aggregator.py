@@ -19,7 +19,8 @@ from garfield_amd import aggregators
 _RULES = {"Average": "average", "Median": "median", "Krum": "krum", "Brute": "brute", "Aksel": "aksel",
           "Condense": "condense", "Bulyan": "bulyan", "TrimmedMean": "trimmed-mean",
           "AverageNan": "average-nan", "AveragedMedian": "averaged-median",
-          "GeoMed": "geomed", "NNM-Krum": "nnm-krum", "NNM-GeoMed": "nnm-geomed", "NNM-Average": "nnm-average"}
+          "GeoMed": "geomed", "NNM-Krum": "nnm-krum", "NNM-GeoMed": "nnm-geomed", "NNM-Average": "nnm-average",
+          "CClip": "cclip", "NNM-CClip": "nnm-cclip"}
 
 
 class Aggregator_tf:

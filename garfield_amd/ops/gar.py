@@ -10,7 +10,9 @@ current stream, nothing copied to the host:
 
 * Krum / Multi-Krum: split-K MFMA Gram -> one-workgroup selection -> combine;
 * Geometric median: Gram -> one-workgroup smoothed Weiszfeld on the n x n distances -> combine;
-* Nearest-neighbour mixing before Krum / geometric median / average: Gram -> one-workgroup mix
+* Centered clipping: Gram -> (Krum selection as the robust start) -> one-workgroup clipping rounds on the
+  n x n distances -> combine;
+* Nearest-neighbour mixing before Krum / geometric median / centered clipping / average: Gram -> one-workgroup mix
   (neighbour sets + the mixed rows' pseudo-Gram) -> the rule's selection -> un-mix -> combine;
 * Bulyan: Gram -> on-device selection loop -> W[t, n] -> fused W·G averaged-median;
 * Brute: Gram -> device-wide subset search (atomicMin on (diameter, rank)) -> combine;
@@ -389,12 +391,151 @@ def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> tor
     return _combine_rows(rows, _geomed_w(rows, iters, nu))
 
 
+# Centered clipping (CC; docs/GAR_SEMANTICS.md): v <- v + (1/n) Σ_i (x_i - v) min(1, tau / ||x_i - v||). The
+# centre stays an affine combination of the rows, so the rounds run on the Gram's distances alone and
+# end in a weight vector for the combine kernels. tau=None: the radius from the data, every round (the
+# (|V| - f)-th smallest distance of the centre to a worker).
+
+CCLIP_STARTS = ("mean", "krum")
+
+
+def _cclip_args(n: int, f: int, tau, iters, start, m: int | None = None) -> tuple:
+    """(tau as the launchers take it, iters, m): validates centered clipping's own arguments."""
+    if iters is None or int(iters) < 1:
+        raise ValueError(f"cclip: expected iters >= 1, got {iters}")
+    if tau is not None and not float(tau) > 0.0:
+        raise ValueError(f"cclip: expected tau None (from the data) or > 0, got {tau}")
+    if f < 0:
+        raise ValueError(f"cclip: expected f >= 0, got {f}")
+    if isinstance(start, str):
+        if start not in CCLIP_STARTS:
+            raise ValueError(f"cclip: unknown start {start!r}; available: {CCLIP_STARTS} or an [n] weight tensor")
+        if start == "krum":
+            m = n - f - 2 if m is None else m
+            if n < 2 * f + 3 or not 1 <= m <= n - f - 2:   # Krum's own requirement, as on every other path
+                raise ValueError(f"cclip: start='krum' expects n >= 2f + 3 and 1 <= m <= n - f - 2, got n = {n}, "
+                                 f"f = {f}, m = {m}")
+    elif not isinstance(start, torch.Tensor) or start.numel() != n:
+        raise ValueError(f"cclip: start must be one of {CCLIP_STARTS} or an [n] weight tensor (n = {n})")
+    return (0.0 if tau is None else float(tau)), int(iters), m
+
+
+def cclip_select(C, ws: Workspace, g: torch.Tensor, n: int, nw: int, f: int, tau: float, iters: int, start="mean",
+                 m: int | None = None) -> torch.Tensor:
+    """Centered-clipping weights [n] from a device Gram ``g`` (pitch gram_padded(n), n <= MAX_ROWS; rows
+    nw..n-1 basis-only): for ``start="krum"`` k_krum_select writes the start into the weights buffer, then
+    k_cclip_select iterates in place. ``tau <= 0``: from the data. Every buffer comes from ``ws``
+    (capture-safe)."""
+    w = ws.get("weights", n)
+    a0 = None
+    if isinstance(start, torch.Tensor):
+        a0 = ws.get("cclip_a0", n)
+        a0.copy_(start.reshape(-1))
+    elif start == "center":   # all the start weight on the appended centre row
+        a0 = ws.tensors.get("cclip_center")
+        if a0 is None:
+            a0 = ws.tensors["cclip_center"] = _one_hot_last(n, g.device)
+    elif start == "krum":
+        C.gpu_krum_select(g, n, f, m, w, ws.get("order", n, torch.int32), ws.get("scores", n))
+        a0 = w
+    C.gpu_cclip_select(g, n, nw, a0, tau, f, iters, w, ws.get("cclip_dists", n))
+    return w
+
+
+def _one_hot_last(n: int, device) -> torch.Tensor:
+    e = torch.zeros(n, dtype=torch.float32, device=device)
+    e[-1] = 1.0
+    return e
+
+
+def cclip_weights_from_distances(C, D: torch.Tensor, nw: int, f: int, tau: float, iters: int, start="mean",
+                                 m: int | None = None) -> torch.Tensor:
+    """Centered-clipping weights [n] (fp32, CPU) from squared distances: the C++ path, else the oracle.
+    ``tau <= 0``: from the data."""
+    a0 = None
+    if isinstance(start, str) and start == "center":
+        start = _one_hot_last(D.shape[0], "cpu")
+    if isinstance(start, torch.Tensor):
+        a0 = start.reshape(-1).double().cpu()
+    elif start == "krum":
+        a0 = (C.cpu_krum_weights(D, f, m)[0] if C is not None else ref.krum_weights(D, f, m)).double()
+    if C is None:
+        return ref.cclip_weights(D, nw, a0, tau if tau > 0 else None, f, iters).float()
+    return C.cpu_cclip_weights(D, nw, a0, tau, f, iters)
+
+
+def _with_center(rows: Rows, center: torch.Tensor) -> Rows:
+    """The row table with ``center`` appended as row n (cast to the rows' dtype; the rows are not copied)."""
+    c = center.detach().reshape(-1)
+    if c.numel() != rows.d:
+        raise ValueError(f"cclip: center has {c.numel()} elements, the gradients {rows.d}")
+    c = c.to(device=rows.device, dtype=rows.dtype)
+    table = list(rows.obj.unbind(0)) if isinstance(rows.obj, torch.Tensor) else list(rows.obj)
+    out = prepare(table + [c])
+    out.out_dtype = rows.out_dtype
+    return out
+
+
+def _cclip_w(rows: Rows, nw: int, f: int, tau: float, iters: int, start, m: int | None) -> torch.Tensor:
+    n = rows.n
+    if n > MAX_ROWS:   # the Gram's own device: large_gram on the GPU, no host round trip
+        g = _large_gram(rows)
+        a0 = start if isinstance(start, torch.Tensor) else None
+        if isinstance(start, str) and start == "center":
+            a0 = _one_hot_last(n, g.device)
+        elif isinstance(start, str) and start == "krum":
+            a0 = large_select(g, f, m) if g.is_cuda else krum_weights_from_gram(g, f, m)
+        return cclip_weights_from_gram(g, nw, a0, tau if tau > 0 else None, f, iters)
+    C = _C_for(rows)
+    if rows.device.type == "cuda":
+        ws = workspace(rows)
+        return cclip_select(C, ws, _gram_into(C, rows, ws), n, nw, f, tau, iters, start, m)
+    D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
+    return cclip_weights_from_distances(C, D, nw, f, tau, iters, start, m)
+
+
+def _cclip_rows_w(gradients, f, tau, iters, start, center, m, pre) -> tuple:
+    rows = prepare(gradients)
+    if center is not None:
+        if start is not None:
+            raise ValueError("cclip: give either center or start, not both")
+        if pre is not None:
+            raise ValueError("cclip: a center is not supported under nearest-neighbour mixing")
+        tau_, iters, m = _cclip_args(rows.n, f, tau, iters, "mean", m)
+        rows = _with_center(rows, center)
+        return rows, _cclip_w(rows, rows.n - 1, f, tau_, iters, "center", m)
+    start = "mean" if start is None else start
+    if pre is not None:
+        return rows, _nnm_w(rows, f, "cclip", _pre=pre, m=m, iters=iters, tau=tau, start=start)
+    tau_, iters, m = _cclip_args(rows.n, f, tau, iters, start, m)
+    return rows, _cclip_w(rows, rows.n, f, tau_, iters, start, m)
+
+
+def cclip_weights(gradients, f: int = 0, tau: float | None = None, iters: int = 3, start=None, center=None,
+                  m: int | None = None, pre: str | None = None) -> torch.Tensor:
+    """Weights of centered clipping ([n] fp32 on the gradients' device; [n + 1] with a ``center``, whose
+    row is the last): ``iters`` clipping rounds iterated on the pairwise distances alone. ``tau``: the
+    absolute L2 radius, None: from the data (the (n - f)-th smallest distance to the centre, every round).
+    ``start``: "mean" (default), "krum" (the Multi-Krum weights with ``f`` and ``m``: the robust start) or an
+    [n] weight tensor; ``center``: a d-vector to start from instead. ``pre="nnm"``: the row weights of
+    centered clipping on the rows mixed over their ``n - f`` nearest (:func:`nnm_weights`)."""
+    return _cclip_rows_w(gradients, f, tau, iters, start, center, m, pre)[1]
+
+
+def cclip(gradients, f: int = 0, tau: float | None = None, iters: int = 3, start=None, center=None,
+          m: int | None = None, pre: str | None = None, **_) -> torch.Tensor:
+    """Centered clipping (Karimireddy et al., 2021): Σ_i a_i g_i (+ a_n center) with the weights of
+    :func:`cclip_weights`."""
+    rows, w = _cclip_rows_w(gradients, f, tau, iters, start, center, m, pre)
+    return _combine_rows(rows, w)
+
+
 # Nearest-neighbour mixing (NNM; docs/GAR_SEMANTICS.md): every row is replaced by the mean of its
 # n - f nearest rows, itself included, before the rule runs. Mixing is linear: the mixed rows' distances
 # follow from the Gram, the rule's weights fold back onto the original rows, and the combine kernels
 # consume those: no pass over the d-length rows, no [n, d] buffer of mixed gradients.
 
-NNM_RULES = ("krum", "geomed", "average")
+NNM_RULES = ("krum", "geomed", "cclip", "average")
 
 
 def _nnm_args(n: int, f: int, rule: str, pre: str = "nnm", m: int | None = None, iters: int = 32,
@@ -413,10 +554,11 @@ def _nnm_args(n: int, f: int, rule: str, pre: str = "nnm", m: int | None = None,
 
 
 def nnm_select(C, ws: Workspace, g: torch.Tensor, n: int, f: int, rule: str, m: int | None = None, iters: int = 32,
-               nu: float = 1e-6) -> torch.Tensor:
+               nu: float = 1e-6, cclip: tuple | None = None) -> torch.Tensor:
     """Row weights [n] of ``rule`` after the mixing, from a device Gram ``g`` (pitch gram_padded(n),
     n <= MAX_ROWS): k_nnm_mix -> the rule's own selection on the pseudo-Gram -> k_nnm_unmix. Every
-    buffer comes from ``ws`` (capture-safe)."""
+    buffer comes from ``ws`` (capture-safe). ``cclip``: centered clipping's (tau, iters, start) of
+    :func:`_cclip_args`, the start computed on the mixed rows."""
     np_ = C.gram_padded(n)
     H = ws.get("nnm_H", np_ * np_)
     masks = ws.get("nnm_masks", 2 * n, torch.int64)
@@ -427,6 +569,8 @@ def nnm_select(C, ws: Workspace, g: torch.Tensor, n: int, f: int, rule: str, m: 
     elif rule == "geomed":
         a = ws.get("weights", n)
         C.gpu_geomed_select(H, n, iters, nu, a, ws.get("geomed_dists", n))
+    elif rule == "cclip":
+        a = cclip_select(C, ws, H, n, n, f, cclip[0], cclip[1], cclip[2], m)
     else:
         a = ws.tensors.get("avg_w")
         if a is None:
@@ -473,38 +617,56 @@ def _nnm_fold(S: torch.Tensor, a: torch.Tensor, c: int) -> torch.Tensor:
     return (acc / a.sum().clamp(min=torch.finfo(torch.float64).tiny) / c).float()
 
 
-def _nnm_w(rows: Rows, f: int, rule: str, _pre: str = "nnm", **kw) -> torch.Tensor:
+def _nnm_w(rows: Rows, f: int, rule: str, _pre: str = "nnm", tau=None, start="mean", **kw) -> torch.Tensor:
     n = rows.n
+    cc = None
+    if rule == "cclip":
+        kw.setdefault("iters", 3)
+        if not isinstance(start, str):
+            raise ValueError(f"nnm-cclip: start must be one of {CCLIP_STARTS}")
     m, iters, nu = _nnm_args(n, f, rule, _pre, **kw)
+    if rule == "cclip":
+        tau_, iters, m = _cclip_args(n, f, tau, iters, start, m)
+        cc = (tau_, iters, start)
     if n > MAX_ROWS:
         H, S = nnm_from_gram(_large_gram(rows), f)
         if rule == "krum":
             a = large_select(H, f, m) if H.is_cuda else krum_weights_from_gram(H, f, m)
         elif rule == "geomed":
             a = geomed_weights_from_gram(H, iters, nu)
+        elif rule == "cclip":
+            a0 = None
+            if start == "krum":
+                a0 = large_select(H, f, m) if H.is_cuda else krum_weights_from_gram(H, f, m)
+            a = cclip_weights_from_gram(H, n, a0, tau, f, iters)
         else:
             a = torch.full((n,), 1.0 / n, dtype=torch.float32, device=H.device)
         return _nnm_fold(S, a, n - f)
     C = _C_for(rows)
     if rows.device.type == "cuda":
         ws = workspace(rows)
-        return nnm_select(C, ws, _gram_into(C, rows, ws), n, f, rule, m, iters, nu)
+        return nnm_select(C, ws, _gram_into(C, rows, ws), n, f, rule, m, iters, nu, cc)
     D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
-    return nnm_weights_from_distances(C, D, f, rule, m, iters, nu)
+    return nnm_weights_from_distances(C, D, f, rule, m, iters, nu, cc)
 
 
 def nnm_weights_from_distances(C, D: torch.Tensor, f: int, rule: str, m: int | None = None, iters: int = 32,
-                               nu: float = 1e-6) -> torch.Tensor:
+                               nu: float = 1e-6, cclip: tuple | None = None) -> torch.Tensor:
     """Row weights [n] (fp32, CPU) of ``rule`` after the mixing, from squared distances: the C++ path
-    (n <= MAX_ROWS: the sets are two mask words), else the oracle."""
+    (n <= MAX_ROWS: the sets are two mask words), else the oracle. ``cclip`` as in :func:`nnm_select`."""
     n = D.shape[0]
     if C is None or n > MAX_ROWS:
+        if rule == "cclip":
+            return ref.nnm_weights(D, f, rule, m=m, iters=cclip[1], tau=cclip[0] if cclip[0] > 0 else None,
+                                   start=cclip[2])
         return ref.nnm_weights(D, f, rule, m=m, iters=iters, nu=nu)
     Dm, masks = C.cpu_nnm_mix(D, f)
     if rule == "krum":
         a = C.cpu_krum_weights(Dm, f, m)[0]
     elif rule == "geomed":
         a = C.cpu_geomed_weights(Dm, iters, nu)
+    elif rule == "cclip":
+        a = cclip_weights_from_distances(C, Dm, n, f, cclip[0], cclip[1], cclip[2], m)
     else:
         a = torch.full((n,), 1.0 / n, dtype=torch.float32)
     return C.cpu_nnm_unmix(a, masks, n - f)
@@ -546,7 +708,7 @@ def masks_from_sets(sets) -> torch.Tensor:
 
 def nnm_weights(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
     """Weights over the ORIGINAL rows ([n] fp32 on the gradients' device) of ``rule`` (krum: ``m``;
-    geomed: ``iters``, ``nu``; average) applied to the rows mixed over their n - f nearest."""
+    geomed: ``iters``, ``nu``; cclip: ``tau``, ``iters``, ``start`` "mean" / "krum", ``m``; average) applied to the rows mixed over their n - f nearest."""
     return _nnm_w(prepare(gradients), f, rule, **kw)
 
 
@@ -826,6 +988,48 @@ def geomed_weights_from_gram(g: torch.Tensor, iters: int = 32, nu: float = 1e-6)
     return a.float()
 
 
+def cclip_weights_from_gram(g: torch.Tensor, nw: int | None = None, a0: torch.Tensor | None = None,
+                            tau: float | None = None, f: int = 0, iters: int = 3) -> torch.Tensor:
+    """Centered-clipping weights [n] (fp32, g's device) from a Gram matrix (vectorised in fp64, any n, no
+    host round trip): reference.cclip_weights with the distances built as the selection kernels build
+    them. Rows nw..n-1 are basis-only; ``a0`` None: uniform on the workers; ``tau`` None: from the data."""
+    n = g.shape[0]
+    nw = n if nw is None else nw
+    D = distances_from_gram(g).double()
+    D.fill_diagonal_(0.0)
+    fin = torch.isfinite(D)
+    fin.fill_diagonal_(False)
+    valid = fin.any(1)
+    D = torch.where(fin, D, torch.zeros_like(D))
+    zero = torch.zeros((), dtype=torch.float64, device=g.device)
+    is_worker = torch.arange(n, device=g.device) < nw
+    V = valid & is_worker
+    nv = V.sum()
+    nvd = nv.clamp(min=1).double()
+    uniform = torch.where(V, 1.0 / nvd, zero)
+    if a0 is None:
+        a = uniform
+    else:
+        a = torch.where(valid, a0.to(g.device, torch.float64).reshape(-1), zero)
+        tot = a.sum()
+        ok = torch.isfinite(tot) & (tot > 0)
+        a = torch.where(ok, a / torch.where(ok, tot, torch.ones_like(tot)), uniform)
+    k = (nv - f).clamp(min=1)
+    for _ in range(iters):
+        s = (D * a[None, :]).sum(1)
+        q = 0.5 * (a * s).sum()
+        r = (s - q).clamp(min=0).sqrt()
+        if tau is None:   # the k-th smallest r over V: only its value is used
+            t = torch.sort(torch.where(V, r, torch.full_like(r, math.inf))).values.gather(0, (k - 1).reshape(1))[0]
+        else:
+            t = torch.full((), float(tau), dtype=torch.float64, device=g.device)
+        lam = torch.where(V & (r > t), t / r, V.double())
+        a = a * (1.0 - lam.sum() / nvd) + lam / nvd
+    # no valid worker (n == 1, every pair non-finite): uniform on the workers, without a host branch on device data
+    a = torch.where(nv > 0, a, torch.where(is_worker, 1.0 / nw, zero))
+    return a.float()
+
+
 def _stable_order(v: torch.Tensor) -> torch.Tensor:
     """Indices by (value, index), NaN last: reference._order."""
     return torch.sort(_nan_inf(v), stable=True).indices
@@ -903,6 +1107,9 @@ RULES = {
     "brute": brute,
     "aksel": aksel,
     "geomed": geomed,
+    "cclip": cclip,
+    "nnm-cclip": lambda gradients, f=0, tau=None, iters=3, start="mean", m=None, **_: nnm(
+        gradients, f, "cclip", tau=tau, iters=iters, start=start, m=m),
     "nnm-krum": lambda gradients, f, m=None, **_: nnm(gradients, f, "krum", m=m),
     "nnm-geomed": lambda gradients, f=0, iters=32, nu=1e-6, **_: nnm(gradients, f, "geomed", iters=iters, nu=nu),
     "nnm-average": lambda gradients, f=0, **_: nnm(gradients, f, "average"),

@@ -129,6 +129,74 @@ def geomed(G, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
     return combine(G, geomed_weights(pairwise_sqdist(G), iters, nu))
 
 
+def cclip_weights(D: torch.Tensor, nw: int | None = None, a0=None, tau: float | None = None, f: int = 0,
+                  iters: int = 3) -> torch.Tensor:
+    """Weights [n] (fp64) of centered clipping, iterated on the squared distances alone
+    (docs/GAR_SEMANTICS.md "Centered clipping"): the centre v = Σ a_j x_j has
+    ||x_i - v||² = Σ_j a_j D_ij - ½ Σ_jk a_j a_k D_jk, and one round is
+    a_j <- a_j (1 - Λ/|V|) + λ_j/|V| with λ_i = min(1, τ / r_i) on the valid workers. Rows nw..n-1 are
+    basis-only. ``a0``: the start weights (None: uniform on the workers); ``tau``: the radius (None: the
+    max(|V| - f, 1)-th smallest r of the round). Exactly ``iters`` rounds, sums in index order."""
+    D = D.detach().to(device="cpu", dtype=torch.float64)
+    n = D.shape[0]
+    nw = n if nw is None else nw
+    fin = [[i != j and math.isfinite(float(D[i, j])) for j in range(n)] for i in range(n)]
+    valid = [i for i in range(n) if any(fin[i])]
+    V = [i for i in valid if i < nw]
+    if not V:
+        return torch.tensor([1.0 / nw if i < nw else 0.0 for i in range(n)], dtype=torch.float64)
+    dist = [[float(D[i, j]) if fin[i][j] else 0.0 for j in range(n)] for i in range(n)]
+    a = [0.0] * n
+    tot = 0.0
+    if a0 is not None:
+        for i in valid:
+            a[i] = float(a0[i])
+            tot += a[i]
+    if a0 is not None and math.isfinite(tot) and tot > 0.0:
+        a = [x / tot for x in a]
+    else:
+        a = [1.0 / len(V) if i in V else 0.0 for i in range(n)]
+    k = max(len(V) - f, 1)
+    for _ in range(iters):
+        s = [0.0] * n
+        for i in valid:
+            acc = 0.0
+            for j in valid:
+                acc += a[j] * dist[i][j]
+            s[i] = acc
+        q = 0.0
+        for i in valid:
+            q += a[i] * s[i]
+        q *= 0.5
+        r = {i: math.sqrt(max(s[i] - q, 0.0)) for i in V}
+        t = sorted(r.values())[k - 1] if tau is None else float(tau)
+        lam, Lam = [0.0] * n, 0.0
+        for i in V:
+            lam[i] = 1.0 if r[i] <= t else t / r[i]
+            Lam += lam[i]
+        keep = 1.0 - Lam / len(V)
+        a = [a[i] * keep + lam[i] / len(V) for i in range(n)]
+    return torch.tensor(a, dtype=torch.float64)
+
+
+def cclip(G, f: int = 0, tau: float | None = None, iters: int = 3, start="mean", center=None,
+          m: int | None = None) -> torch.Tensor:
+    """Centered clipping of the rows G: ``start`` "mean", "krum" (the Multi-Krum weights, f and m) or an
+    [n] weight vector; ``center``: a d-vector appended as a basis-only row that carries the start."""
+    X = _g(G)
+    n = X.shape[0]
+    if center is not None:
+        X = torch.cat([X, center.detach().reshape(1, -1).to(device="cpu", dtype=torch.float64)])
+    D = pairwise_sqdist(X)
+    if center is not None:
+        a0 = [0.0] * n + [1.0]
+    elif isinstance(start, str):
+        a0 = {"mean": lambda: None, "krum": lambda: krum_weights(D, f, m)}[start]()
+    else:
+        a0 = start
+    return combine(X, cclip_weights(D, n, a0, tau, f, iters))
+
+
 # Nearest-neighbour mixing (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing"): every gradient is
 # replaced by the mean of its c = n - f nearest gradients, itself included, before a rule runs.
 # Mixing is linear, so everything below works on the squared distances alone.
@@ -216,10 +284,13 @@ def nnm_weights(D: torch.Tensor, f: int, rule: str = "krum", **kw) -> torch.Tens
         a = krum_weights(Dm, f, kw.get("m"))
     elif rule == "geomed":
         a = geomed_weights(Dm, kw.get("iters", 32), kw.get("nu", 1e-6))
+    elif rule == "cclip":   # start "mean" or "krum", on the mixed rows
+        a0 = krum_weights(Dm, f, kw.get("m")) if kw.get("start", "mean") == "krum" else None
+        a = cclip_weights(Dm, n, a0, kw.get("tau"), f, kw.get("iters", 3))
     elif rule == "average":
         a = torch.full((n,), 1.0 / n, dtype=torch.float64)
     else:
-        raise ValueError(f"nnm: unsupported rule {rule!r} (krum, geomed, average)")
+        raise ValueError(f"nnm: unsupported rule {rule!r} (krum, geomed, cclip, average)")
     return nnm_row_weights(sets, a)
 
 

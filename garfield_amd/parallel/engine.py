@@ -49,10 +49,10 @@ from garfield_amd.utils.profiling import PhaseTimer
 # the first convolution; users may override the variable explicitly.
 os.environ.setdefault("MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_WRW_XDLOPS", "0")
 
-WEIGHTED_RULES = {"average", "krum", "brute", "aksel", "geomed"}
+WEIGHTED_RULES = {"average", "krum", "brute", "aksel", "geomed", "cclip"}
 _LP_MODULES = (nn.modules.conv._ConvNd, nn.Linear)
 COORD_RULES = {"median", "trimmed-mean", "averaged-median", "average-nan", "condense", "bulyan"}
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed"}   # per-layer != flat only for distance-based rules
+LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip"}   # per-layer != flat only for distance-based rules
 # Layer-wise Krum as device operations (gar_layerwise.hip: one segmented Gram launch, a batched
 # selection, one segmented combine + SGD); "0" runs the per-segment loop (the reference form).
 LW_DEVICE = os.environ.get("GARFIELD_LW_DEVICE", "1") != "0"
@@ -102,7 +102,7 @@ class EngineConfig:
     gar_kwargs: dict = field(default_factory=dict)
     # "nnm": nearest-neighbour mixing before the rule (every gradient replaced by the mean of its
     # n - f nearest, itself included; docs/GAR_SEMANTICS.md), folded into the rule's row weights, for
-    # gar in {krum, geomed, average}: the flat step (GPU, CPU, n > 128), explicit row lists and the
+    # gar in {krum, geomed, cclip, average}: the flat step (GPU, CPU, n > 128), explicit row lists and the
     # sharded flat selection. Not yet supported (ValueError at construction): any other rule,
     # layerwise=True, and the sharded path with n > 128 rows on the GPU. None: exactly today's paths.
     pre_aggregation: str | None = None
@@ -438,6 +438,8 @@ class RobustDataParallel:
         if self.cfg.gar == "geomed":
             iters, nu = self._geomed_args(kw)
             return {"iters": iters, "nu": nu}
+        if self.cfg.gar == "cclip":
+            return self._cclip_kwargs(kw)
         return {}
 
     def _check_gar(self) -> None:
@@ -447,6 +449,12 @@ class RobustDataParallel:
         kw = dict(self.cfg.gar_kwargs)
         if self.cfg.m is not None:
             kw["m"] = self.cfg.m
+        if self.cfg.gar == "cclip":
+            if kw.get("center") is not None:   # needs an exchange-dtype copy of the previous aggregate
+                raise ValueError("GAR 'cclip': a center is not supported by the training engine (start: 'mean' or 'krum')")
+            start = kw.get("start", "mean")
+            if not isinstance(start, str) or start not in gar.CCLIP_STARTS:
+                raise ValueError(f"GAR 'cclip': start must be one of {gar.CCLIP_STARTS}, got {kw.get('start')!r}")
         msg = rule.check(gradients=[torch.zeros(1)] * self.n, f=self.cfg.f, **kw)
         if msg is not None:
             raise ValueError(f"GAR {self.cfg.gar!r} with n={self.n}: {msg}")
@@ -542,7 +550,7 @@ class RobustDataParallel:
                 gkw["m"] = cfg.m
             if rule == "condense":
                 gkw.setdefault("seed", cfg.seed + self.step_count)
-            if rule == "geomed" or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
+            if rule in ("geomed", "cclip") or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
                 self.last_weights = w = self._weights(rule, kw, self.G.float())
                 g = gar.combine(self.G.float(), w).float()
             else:
@@ -580,7 +588,7 @@ class RobustDataParallel:
         if cfg.m is not None and rule in ("krum", "bulyan"):
             gkw["m"] = cfg.m
         cuda = self.device.type == "cuda"
-        if cuda and LW_DEVICE and self.n <= gar.MAX_ROWS and (rule in ("krum", "geomed")
+        if cuda and LW_DEVICE and self.n <= gar.MAX_ROWS and (rule in ("krum", "geomed", "cclip")
                                                               or (rule == "bulyan" and self.n <= 64)):
             self._layerwise_device(rule, first)
             return
@@ -657,6 +665,12 @@ class RobustDataParallel:
         if rule == "geomed":
             iters, nu = self._geomed_args(cfg.gar_kwargs)
             C.gpu_geomed_select(lw["gram"], n, iters, nu, lw["w"], lw["dists"], lw["L"])
+        elif rule == "cclip":   # every segment's start (Krum's batched selection) and clipping rounds, in place
+            tau, iters, start = self._cclip_args(cfg.gar_kwargs)
+            if start == "krum":
+                C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
+            C.gpu_cclip_select(lw["gram"], n, n, lw["w"] if start == "krum" else None, tau, f, iters, lw["w"],
+                               lw["dists"], lw["L"])
         else:
             C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
         C.gpu_lw_combine_sgd(G, lw["jobs"], lw["seg_off"], 0, lw["w"], self.flat.data[: self.d], self.mom[: self.d],
@@ -680,12 +694,25 @@ class RobustDataParallel:
             return gar.brute_weights(G, f)
         if rule == "geomed":
             return gar.geomed_weights(G, *self._geomed_args(kw))
+        if rule == "cclip":
+            return gar.cclip_weights(G, f, **self._cclip_kwargs(kw))
         return gar.aksel_weights(G, f, kw.get("mode", "mid"))
 
     @staticmethod
     def _geomed_args(kw: dict) -> tuple:
         """(iters, nu) of the geometric median from the rule's keyword arguments."""
         return int(kw.get("iters", 32)), float(kw.get("nu", 1e-6))
+
+    @staticmethod
+    def _cclip_args(kw: dict) -> tuple:
+        """(tau as the launchers take it: 0 = from the data, iters, start) of centered clipping."""
+        tau = kw.get("tau")
+        return (0.0 if tau is None else float(tau)), int(kw.get("iters", 3)), kw.get("start", "mean")
+
+    def _cclip_kwargs(self, kw: dict) -> dict:
+        """Centered clipping's keyword arguments of gar.cclip_weights / gar.nnm_weights."""
+        return {"tau": kw.get("tau"), "iters": int(kw.get("iters", 3)), "start": kw.get("start", "mean"),
+                "m": self.cfg.m}
 
     def _coordinate(self, rule: str, kw: dict, out: torch.Tensor, G=None) -> None:
         """Coordinate-wise rule (or Bulyan) over ``G`` (default: the [n, d] exchange rows;
@@ -743,6 +770,8 @@ class RobustDataParallel:
                     w = gar.aksel_weights(rows, cfg.f, cfg.gar_kwargs.get("mode", "mid"))
                 elif cfg.gar == "geomed":
                     w = gar.geomed_weights(rows, *self._geomed_args(cfg.gar_kwargs))
+                elif cfg.gar == "cclip":
+                    w = gar.cclip_weights(rows, cfg.f, **self._cclip_kwargs(cfg.gar_kwargs))
                 else:
                     w = torch.full((len(rows),), 1.0 / len(rows), device=self.device)
                 self.last_weights = w
@@ -762,8 +791,8 @@ class RobustDataParallel:
             # as a [rows, d] fp32 matrix: the aggregate keeps fp32 (a list of 16-bit rows
             # would round it to the rows' dtype), as the synchronous step's
             X = torch.stack([r.float() for r in rows])
-            if cfg.pre_aggregation:
-                self.last_weights = w = gar.nnm_weights(X, cfg.f, cfg.gar, **self._nnm_kwargs(cfg.gar_kwargs))
+            if cfg.pre_aggregation or cfg.gar == "cclip":
+                self.last_weights = w = self._weights(cfg.gar, dict(cfg.gar_kwargs), X)
                 g = gar.combine(X, w).float()
             else:
                 g = gar.aggregate(cfg.gar, X, **self._rule_kwargs()).float()

@@ -61,8 +61,8 @@ from garfield_amd.parallel.comm import collectives_on, gloo_backend, world1_coll
 from garfield_amd.parallel.rccl import direct_backend
 from garfield_amd.parallel.signals import Handoff
 
-DISTANCE_RULES = {"krum", "brute", "bulyan", "geomed"}
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed"}
+DISTANCE_RULES = {"krum", "brute", "bulyan", "geomed", "cclip"}
+LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip"}
 SUPPORTED = DISTANCE_RULES | {"average", "aksel", "median", "trimmed-mean", "averaged-median", "average-nan",
                               "condense"}
 
@@ -78,7 +78,7 @@ def layerwise_device_ok(rule: str, n: int, f: int) -> bool:
         return n - 2 * f - 2 <= 64
     if rule == "brute":
         return n <= 64
-    return True   # krum, geomed (batched one-workgroup selections: n <= MAX_ROWS), aksel
+    return True   # krum, geomed, cclip (batched one-workgroup selections: n <= MAX_ROWS), aksel
 
 
 def shard_pad(world: int, base: int = 64) -> int:
@@ -620,7 +620,7 @@ class ShardedAggregator:
             mats[b.lo] = self._matrix(b)
         if rule == "brute":   # C(n, f) subsets of n > 128 rows: the device search takes n <= 64
             raise ValueError(f"brute: n must be <= 64 on the GPU (n = {n})")
-        if rule in ("krum", "bulyan", "geomed"):
+        if rule in ("krum", "bulyan", "geomed", "cclip"):
             total = None
             for b in self.buckets:
                 g = gar.large_gram(mats[b.lo])                  # MFMA, fp32 (gar_large.hip)
@@ -631,6 +631,10 @@ class ShardedAggregator:
                 ws = gar.large_select(gs, f, m)
             elif rule == "geomed":   # vectorised on the Gram's device: no host round trip
                 ws = gar.geomed_weights_from_gram(gs, *e._geomed_args(kw))
+            elif rule == "cclip":
+                ck = e._cclip_kwargs(kw)
+                a0 = gar.large_select(gs, f, m) if ck["start"] == "krum" else None
+                ws = gar.cclip_weights_from_gram(gs, n, a0, ck["tau"], f, ck["iters"])
             else:
                 W = gar.large_select(gs, f, m, bulyan=True)
                 Wm = torch.empty_like(W)
@@ -684,7 +688,8 @@ class ShardedAggregator:
         ws = self._ws_any()
         m = cfg.m if cfg.m is not None else n - f - 2
         if cfg.pre_aggregation:   # after the partial Grams are summed over ranks: the same w on every rank
-            return gar.nnm_select(C, ws, gram_total, n, f, rule, m, *self.e._geomed_args(cfg.gar_kwargs))
+            return gar.nnm_select(C, ws, gram_total, n, f, rule, m, *self.e._geomed_args(cfg.gar_kwargs),
+                                  cclip=self.e._cclip_args(cfg.gar_kwargs))
         if rule == "krum":
             w = ws.get("weights", n)
             order = ws.get("order", n, torch.int32)
@@ -696,6 +701,8 @@ class ShardedAggregator:
             dists = ws.get("geomed_dists", n)
             C.gpu_geomed_select(gram_total, n, *self.e._geomed_args(cfg.gar_kwargs), w, dists)
             return w
+        if rule == "cclip":
+            return gar.cclip_select(C, ws, gram_total, n, n, f, *self.e._cclip_args(cfg.gar_kwargs), m)
         if rule == "brute":
             if n > 64:
                 raise ValueError("brute: n must be <= 64 on the GPU")
@@ -840,6 +847,12 @@ class ShardedAggregator:
                         C.gpu_brute_select(total[si * np2:(si + 1) * np2], n, f, plan["best"], plan["w"][si])
                 elif rule == "geomed":
                     C.gpu_geomed_select(total, n, *e._geomed_args(cfg.gar_kwargs), plan["w"], plan["dists"], L)
+                elif rule == "cclip":
+                    tau, iters, start = e._cclip_args(cfg.gar_kwargs)
+                    if start == "krum":
+                        C.gpu_krum_select(total, n, f, m, plan["w"], plan["order"], plan["scores"], L)
+                    C.gpu_cclip_select(total, n, n, plan["w"] if start == "krum" else None, tau, f, iters, plan["w"],
+                                       plan["dists"], L)
                 else:
                     C.gpu_krum_select(total, n, f, m, plan["w"], plan["order"], plan["scores"], L)
             e.last_weights = plan["w"]
@@ -876,6 +889,8 @@ class ShardedAggregator:
                 elif rule == "geomed":
                     ga = e._geomed_args(cfg.gar_kwargs)
                     W[si] = (Cn.cpu_geomed_weights(Ds, *ga) if Cn is not None else ref.geomed_weights(Ds, *ga)).float()
+                elif rule == "cclip":
+                    W[si] = gar.cclip_weights_from_distances(Cn, Ds, n, f, *e._cclip_args(cfg.gar_kwargs), m)
                 elif rule == "brute":
                     W[si] = (Cn.cpu_brute_weights(Ds, f) if Cn is not None else ref.brute_weights(Ds, f)).float()
                 else:
@@ -932,7 +947,7 @@ class ShardedAggregator:
             D = self._sum_over_ranks(gar.pairwise_distances(X))
             m = cfg.m if cfg.m is not None else n - f - 2
             if cfg.pre_aggregation:   # the mix runs on the summed distances: the same w on every rank
-                w = gar.nnm_weights_from_distances(C, D, f, rule, m, *e._geomed_args(kw))
+                w = gar.nnm_weights_from_distances(C, D, f, rule, m, *e._geomed_args(kw), cclip=e._cclip_args(kw))
                 e.last_weights = w
                 return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
             if rule == "bulyan":
@@ -947,6 +962,8 @@ class ShardedAggregator:
             elif rule == "geomed":
                 ga = e._geomed_args(kw)
                 w = C.cpu_geomed_weights(D, *ga) if C is not None else ref.geomed_weights(D, *ga).float()
+            elif rule == "cclip":
+                w = gar.cclip_weights_from_distances(C, D, n, f, *e._cclip_args(kw), m)
             else:
                 w = C.cpu_brute_weights(D, f) if C is not None else ref.brute_weights(D, f).float()
             e.last_weights = w

@@ -57,6 +57,15 @@ def add_common(p: argparse.ArgumentParser, ps: bool = True) -> argparse.Argument
     return p
 
 
+def add_worker_momentum(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
+    """``--worker_momentum BETA`` of the applications built on ``parallel.engine`` (``EngineConfig.worker_momentum``).
+    The RPC / gRPC trainers have no worker-side momentum yet and do not take the flag."""
+    p.add_argument("--worker_momentum", type=float, default=0.0, metavar="BETA",
+                   help="worker-side momentum, 0 <= BETA < 1: every worker sends m <- BETA * m + (1 - BETA) * g instead "
+                        "of its gradient (what cclip / nnm assume); 0 = off; normally run with --momentum 0")
+    return p
+
+
 def gar_name(a) -> str:
     """The registry name of ``--gar`` with ``--pre_aggregation`` applied (``nnm-krum``, ...)."""
     pre = getattr(a, "pre_aggregation", None)

@@ -70,6 +70,37 @@ def bench_rule(rule, G, f, iters, warmup):
     return 1000 * (time.perf_counter() - t0) / iters
 
 
+def bench_worker_momentum(k: int, d: int, dt, beta: float, device, iters: int, warmup: int) -> dict:
+    """The worker-momentum pass alone (``ops.worker_momentum.update``, later-step form) on k exchange rows
+    of d coordinates: ms per call and the bytes it moves (row read + written, fp32 state read + written)."""
+    from garfield_amd.ops import worker_momentum
+
+    ld = ((d + 63) // 64) * 64
+    X = torch.randn(k, ld, device=device, dtype=dt)
+    M = torch.randn(k, ld, device=device, dtype=torch.float32)
+
+    def run(times):
+        for _ in range(times):
+            worker_momentum.update(X, M, beta, False, 0, d)
+
+    run(warmup)
+    if X.is_cuda:
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        s.record()
+        run(iters)
+        e.record()
+        torch.cuda.synchronize()
+        ms = s.elapsed_time(e) / iters
+    else:
+        t0 = time.perf_counter()
+        run(iters)
+        ms = 1000 * (time.perf_counter() - t0) / iters
+    nbytes = k * d * (2 * X.element_size() + 8)
+    return {"op": "worker_momentum", "k": k, "d": d, "beta": beta, "ms": round(ms, 4), "bytes": nbytes,
+            "GBps": round(nbytes / ms / 1e6, 1)}
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--n", type=int, nargs="+", default=[8, 16, 32, 64])
@@ -80,8 +111,16 @@ def main(argv=None):
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     p.add_argument("--list-input", action="store_true", help="pass a list of n tensors instead of [n, d]")
+    p.add_argument("--worker_momentum", type=float, default=None, metavar="BETA",
+                   help="time the worker-momentum pass alone instead of the rules, on --n rows (as k) of --d coordinates")
     a = p.parse_args(argv)
     dt = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp16": torch.float16}[a.dtype]
+    if a.worker_momentum is not None:
+        for d in a.d:
+            for n in a.n:
+                res = bench_worker_momentum(n, d, dt, a.worker_momentum, a.device, a.iters, a.warmup)
+                print(json.dumps(dict(res, dtype=a.dtype)), flush=True)
+        return
     for d in a.d:
         for n in a.n:
             ld = ((d + 63) // 64) * 64

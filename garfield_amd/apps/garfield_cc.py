@@ -28,7 +28,7 @@ import time
 import torch
 import torch.nn.functional as F
 
-from garfield_amd.apps.common import str2bool
+from garfield_amd.apps.common import add_worker_momentum, str2bool
 from garfield_amd.data.datasets import CLASSES, DatasetManager
 from garfield_amd.models import build_model
 from garfield_amd.parallel.byzps import ByzantinePSDataParallel, ByzPSConfig
@@ -62,6 +62,7 @@ def parse(argv=None):
     p.add_argument("--loss", default="cross-entropy")
     p.add_argument("--lr", type=float, default=0.1)
     p.add_argument("--momentum", type=float, default=0.9)
+    add_worker_momentum(p)
     p.add_argument("--wd", type=float, default=5e-4)
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--lr_milestones", default=None,
@@ -135,6 +136,8 @@ def main(argv=None, results: dict | None = None):
         common.update(layerwise=True)
     if a.pre_aggregation:
         common.update(pre_aggregation=a.pre_aggregation)
+    if a.worker_momentum:
+        common.update(worker_momentum=a.worker_momentum)
     if byz_mode:
         eng = ByzantinePSDataParallel(model, loss_fn, ctx,
                                       ByzPSConfig(num_ps=a.num_ps, fps=a.fps, mar=mar, ps_attack=a.ps_attack,

@@ -121,6 +121,24 @@ float* fptr(const at::Tensor& t) {
   return t.data_ptr<float>();
 }
 
+// Arguments of gpu_ / cpu_worker_momentum: X [k, >= hi] rows of unit element stride (any row stride),
+// M [k, ld >= hi] contiguous fp32, 0 <= lo <= hi, 0 <= beta < 1. Returns X's dtype code.
+int check_worker_momentum(const at::Tensor& X, const at::Tensor& M, int64_t lo, int64_t hi, double beta, bool gpu) {
+  TORCH_CHECK(X.dim() == 2 && M.dim() == 2 && X.size(0) == M.size(0) && X.size(0) >= 1,
+              "worker_momentum: X [k, >= hi] and M [k, ld] with the same k >= 1");
+  TORCH_CHECK(gpu ? X.device().is_cuda() : X.device().is_cpu(), "worker_momentum: ", gpu ? "GPU" : "CPU", " tensors");
+  TORCH_CHECK(M.device() == X.device(), "worker_momentum: X and M must be on the same device");
+  TORCH_CHECK(X.size(1) == 0 || X.stride(1) == 1, "worker_momentum: the rows of X must be contiguous");
+  TORCH_CHECK(X.stride(0) >= 0, "worker_momentum: negative row stride");
+  TORCH_CHECK(M.scalar_type() == at::kFloat && M.is_contiguous(), "worker_momentum: M must be contiguous fp32");
+  const int dt = dtype_code(X);
+  TORCH_CHECK(dt != garfield::kF64, "worker_momentum: fp32, bf16 or fp16 rows");
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= X.size(1) && hi <= M.size(1), "worker_momentum: 0 <= lo <= hi <= row length");
+  TORCH_CHECK(hi < (int64_t{1} << 31) && X.size(0) <= 65535, "worker_momentum: hi < 2^31 and k <= 65535");
+  TORCH_CHECK(beta >= 0.0 && beta < 1.0, "worker_momentum: 0 <= beta < 1");
+  return dt;
+}
+
 // ------------------------------------------------------------------ GPU ----
 
 void g_gram(const RowSet& rs, const at::Tensor& slabs, const at::Tensor& gram) {
@@ -2221,6 +2239,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("rows"), py::arg("peers"), py::arg("empire"), py::arg("param"),
      "Colluding attacks in place on exchanged rows: rows[:peers] are the estimates, rows[peers:] the Byzantine rows "
      "(their honest gradient in, mean + z * std (lie) or -eps * mean (empire) of {own row} + estimates out)");
+  m.def("gpu_worker_momentum", [](const at::Tensor& X, const at::Tensor& M, int64_t lo, int64_t hi, double beta,
+                                  bool first) {
+    const int dt = check_worker_momentum(X, M, lo, hi, beta, true);
+    if (hi <= lo) return;
+    c10::hip::HIPGuard guard(X.device().index());
+    garfield::gpu::worker_momentum(X.data_ptr(), dt, X.stride(0), M.data_ptr<float>(), M.size(1),
+                                   static_cast<int>(X.size(0)), lo, hi, static_cast<float>(beta),
+                                   static_cast<float>(1.0 - beta), first, stream_of(X.device()));
+  }, py::arg("X"), py::arg("M"), py::arg("lo"), py::arg("hi"), py::arg("beta"), py::arg("first"),
+     "Worker-side momentum in place on coordinates [lo, hi) of the k exchange rows X [k, >= hi] (any row stride; "
+     "fp32, bf16 or fp16) with the fp32 state M [k, ld]: m <- g (first) or fmaf(beta, m, (1 - beta) * g), then "
+     "row <- cast(m); a non-finite g stays in the row and leaves m unchanged");
   m.def("gpu_large_combine", &g_large_combine,
         "out = w · x for an [n, d] gradient matrix with n <= LARGE_ROWS (fp32 accumulation); args (x, w, out)");
   m.def("gpu_large_select", &g_large_select, py::arg("gram"), py::arg("f"), py::arg("m"), py::arg("rounds"),
@@ -2725,6 +2755,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return weights_tensor(garfield::cpu::nnm_unmix(floats_from(a), mk, n, c), {n});
   }, py::arg("a"), py::arg("masks"), py::arg("c"),
      "Fold weights over the mixed rows back onto the original rows (fp32 [n])");
+  m.def("cpu_worker_momentum", [](const at::Tensor& X, const at::Tensor& M, int64_t lo, int64_t hi, double beta,
+                                  bool first) {
+    const int dt = check_worker_momentum(X, M, lo, hi, beta, false);
+    if (hi <= lo) return;
+    garfield::cpu::worker_momentum(X.data_ptr(), dt, X.stride(0), M.data_ptr<float>(), M.size(1),
+                                   static_cast<size_t>(X.size(0)), static_cast<size_t>(lo), static_cast<size_t>(hi),
+                                   static_cast<float>(beta), static_cast<float>(1.0 - beta), first);
+  }, py::arg("X"), py::arg("M"), py::arg("lo"), py::arg("hi"), py::arg("beta"), py::arg("first"),
+     "gpu_worker_momentum on the thread pool (fixed chunking, the same fmaf formula: bit-equal state)");
   m.def("cpu_num_threads",[] { return garfield::cpu::pool().size(); });
 
   garfield::mailbox::bind(m);

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <mutex>
 #include <numeric>
@@ -496,6 +497,87 @@ std::vector<double> sqdist_to(const Rows<T>& r, const T* center) {
     out[j] = std::isfinite(s) ? s : kInf;
   }
   return out;
+}
+
+// ---------------------------------------------------------------------------
+// Worker-side momentum (docs/GAR_SEMANTICS.md "Worker momentum"; the kernel: worker_mom.hip)
+
+namespace {
+
+inline uint32_t f32_bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+inline float bits_f32(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
+
+inline float bf16_widen(uint16_t h) { return bits_f32(static_cast<uint32_t>(h) << 16); }
+// round-to-nearest-even of a finite value (a carry out of the mantissa gives the next exponent, up to inf)
+inline uint16_t bf16_round(float f) {
+  const uint32_t u = f32_bits(f);
+  return static_cast<uint16_t>((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+inline float f16_widen(uint16_t h) {
+  const uint32_t sign = static_cast<uint32_t>(h & 0x8000u) << 16, e = (h >> 10) & 0x1fu, m = h & 0x3ffu;
+  if (e == 0) return bits_f32(f32_bits(static_cast<float>(m) * 0x1p-24f) | sign);   // zero and subnormals
+  if (e == 31) return bits_f32(sign | 0x7f800000u | (m << 13));
+  return bits_f32(sign | ((e + 112u) << 23) | (m << 13));
+}
+// round-to-nearest-even of a finite value; 65520 and above give inf
+inline uint16_t f16_round(float f) {
+  uint32_t u = f32_bits(f);
+  const uint16_t sign = static_cast<uint16_t>((u >> 16) & 0x8000u);
+  u &= 0x7fffffffu;
+  if (u >= 0x47800000u) return sign | 0x7c00u;
+  if (u < 0x38800000u)   // below 2^-14: the sum with 0.5 rounds the subnormal mantissa in place
+    return sign | static_cast<uint16_t>(f32_bits(bits_f32(u) + 0.5f) - 0x3f000000u);
+  const uint32_t odd = (u >> 13) & 1u;
+  u += 0xc8000fffu + odd;   // exponent bias 127 -> 15, and the rounding bias
+  return sign | static_cast<uint16_t>(u >> 13);
+}
+
+template <int DT> struct RowElem;
+template <> struct RowElem<kF32> {
+  using type = float;
+  static float widen(float v) { return v; }
+  static float round(float m) { return m; }
+};
+template <> struct RowElem<kBF16> {
+  using type = uint16_t;
+  static float widen(uint16_t v) { return bf16_widen(v); }
+  static uint16_t round(float m) { return bf16_round(m); }
+};
+template <> struct RowElem<kF16> {
+  using type = uint16_t;
+  static float widen(uint16_t v) { return f16_widen(v); }
+  static uint16_t round(float m) { return f16_round(m); }
+};
+
+template <int DT>
+void worker_momentum_t(void* X, int64_t xstride, float* M, int64_t ld, size_t k, size_t lo, size_t hi, float beta,
+                       float omega, bool first) {
+  using E = typename RowElem<DT>::type;
+  parallel_for(lo, hi, default_chunks(hi - lo), [&](size_t, size_t a, size_t b) {
+    for (size_t r = 0; r < k; ++r) {
+      E* row = static_cast<E*>(X) + static_cast<int64_t>(r) * xstride;
+      float* m = M + static_cast<int64_t>(r) * ld;
+      for (size_t x = a; x < b; ++x) {
+        const float g = RowElem<DT>::widen(row[x]);
+        if (!std::isfinite(g)) continue;   // the row keeps it, the state stays
+        const float prod = omega * g;
+        m[x] = first ? g : std::fmaf(beta, m[x], prod);
+        row[x] = RowElem<DT>::round(m[x]);
+      }
+    }
+  });
+}
+
+}  // namespace
+
+void worker_momentum(void* X, int dt, int64_t xstride, float* M, int64_t ld, size_t k, size_t lo, size_t hi, float beta,
+                     float omega, bool first) {
+  if (k == 0 || hi <= lo) return;
+  if (dt == kF32) worker_momentum_t<kF32>(X, xstride, M, ld, k, lo, hi, beta, omega, first);
+  else if (dt == kBF16) worker_momentum_t<kBF16>(X, xstride, M, ld, k, lo, hi, beta, omega, first);
+  else if (dt == kF16) worker_momentum_t<kF16>(X, xstride, M, ld, k, lo, hi, beta, omega, first);
+  else throw std::invalid_argument("worker_momentum: fp32, bf16 or fp16 rows");
 }
 
 #define GARFIELD_INSTANTIATE(T)                                                                          \

@@ -58,5 +58,13 @@ void coordwise(const Rows<T>& r, int mode, size_t f, size_t beta, const std::vec
 // dist_j = ||g_j - center||^2
 template <class T> std::vector<double> sqdist_to(const Rows<T>& r, const T* center);
 
+// Worker-side momentum in place on coordinates [lo, hi) of k rows (docs/GAR_SEMANTICS.md): X row r at
+// X + r * xstride elements of dtype dt (garfield::DType: f32 / bf16 / f16), the fp32 state M row r at
+// M + r * ld. First step: m <- g; later: m <- fmaf(beta, m, omega * g); then row <- the state rounded
+// to nearest even. A non-finite g stays in the row and leaves m unchanged. Fixed chunking; the same
+// formula as the HIP kernel (worker_mom.hip): equal inputs give equal bits.
+void worker_momentum(void* X, int dt, int64_t xstride, float* M, int64_t ld, size_t k, size_t lo, size_t hi, float beta,
+                     float omega, bool first);
+
 }  // namespace cpu
 }  // namespace garfield

@@ -133,6 +133,13 @@ void collude(const RowTable& rows, int P, int T, int64_t d, int dt, bool empire,
 void aksel_select(const float* slabs, int grid, int n, int c, float* weights, float* dists,
                   hipStream_t stream);
 
+// ---- Worker-side momentum (worker_mom.hip), in place on coordinates [lo, hi) of k exchange rows ----
+// X: row r at X + r * xstride elements of dtype dt (f32 / bf16 / f16); M: the fp32 state, row r at
+// M + r * ld. First step: m <- g; later: m <- fmaf(beta, m, omega * g); then row <- cast(m). A
+// non-finite g stays in the row and leaves m unchanged. k <= 65535, hi < 2^31.
+void worker_momentum(void* X, int dt, int64_t xstride, float* M, int64_t ld, int k, int64_t lo, int64_t hi, float beta,
+                     float omega, bool first, hipStream_t stream);
+
 // ---- Split-K partial sums -> exchange rows (gar_flatten.hip) -----------------
 // out[g * ostride + r * opitch + c] = Σ_s part[s * ss + g * gs + r * ipitch + c] (cast to odt),
 // r < R, c < Cc, g < G.

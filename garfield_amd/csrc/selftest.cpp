@@ -163,6 +163,27 @@ static void test_cclip() {
   CHECK(std::fabs(v - (2.575 + 0.25 * (-2.575 - 2.475 - 2.375 + 2.575))) < 1e-5);
 }
 
+// Worker momentum on exactly sized buffers (an access outside them is the sanitizer's to find): bf16
+// rows with a row stride, a range inside the row; powers of two make every value exact.
+static void test_worker_momentum() {
+  const size_t k = 3, ld = 10007, stride = 2 * ld, lo = 3, hi = ld - 2;
+  std::vector<uint16_t> X(k * stride, 0x4000);   // bf16 2.0 everywhere
+  std::vector<float> M(k * ld, 4.0f);
+  X[1 * stride + 100] = 0x7fc0;                  // NaN: stays in the row, out of the state
+  cpu::worker_momentum(X.data(), kBF16, static_cast<int64_t>(stride), M.data(), static_cast<int64_t>(ld), k, lo, hi,
+                       0.5f, 0.5f, false);
+  for (size_t r = 0; r < k; ++r)
+    for (size_t x = 0; x < ld; ++x) {
+      const bool in = x >= lo && x < hi, nan = r == 1 && x == 100;
+      CHECK(M[r * ld + x] == (in && !nan ? 3.0f : 4.0f));                       // 0.5 * 4 + 0.5 * 2
+      CHECK(X[r * stride + x] == (nan ? 0x7fc0 : (in ? 0x4040 : 0x4000)));      // bf16 3.0 inside the range
+      CHECK(X[r * stride + ld + x] == 0x4000);                                  // the other half of the stride
+    }
+  cpu::worker_momentum(X.data(), kBF16, static_cast<int64_t>(stride), M.data(), static_cast<int64_t>(ld), k, 0, 1, 0.5f,
+                       0.5f, true);
+  CHECK(M[0] == 2.0f && M[1] == 4.0f && X[0] == 0x4000);                        // first step: m <- g
+}
+
 static void test_mailbox() {
   mailbox::Mailbox mb(8, 4096, false);
   std::vector<std::thread> writers;
@@ -188,6 +209,7 @@ int main() {
   test_gars();
   test_nnm();
   test_cclip();
+  test_worker_momentum();
   test_mailbox();
   if (failures) {
     std::fprintf(stderr, "selftest: %d failure(s)\n", failures);

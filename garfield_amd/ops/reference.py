@@ -423,6 +423,21 @@ def brute(G, f: int) -> torch.Tensor:
     return combine(G, brute_weights(pairwise_sqdist(G), f))
 
 
+def worker_momentum(X, M, beta: float, first: bool, lo: int = 0, hi: int | None = None):
+    """Worker-side momentum on coordinates [lo, hi) of the rows ``X`` [k, >= hi] with the state ``M``
+    [k, >= hi] (docs/GAR_SEMANTICS.md "Worker momentum"): ``(state, finite)``, both [k, hi - lo]. The
+    new state in exact fp64 arithmetic, m <- g on the first step and beta * m + (1 - beta) * g later,
+    with g the row's value; where g is not finite (``finite`` False) the state stays what it was and
+    the row keeps g. The row a native implementation leaves is ITS fp32 state rounded to nearest even
+    into the row's dtype, never this fp64 value rounded."""
+    X, M = _g(X), _g(M)
+    hi = X.shape[1] if hi is None else hi
+    g, m = X[:, lo:hi], M[:, lo:hi]
+    finite = torch.isfinite(g)
+    new = g if first else beta * m + (1.0 - beta) * g
+    return torch.where(finite, new, m), finite
+
+
 def aksel(G, f: int, mode: str = "mid") -> torch.Tensor:
     X = _g(G)
     n = X.shape[0]

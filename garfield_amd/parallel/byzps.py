@@ -54,6 +54,8 @@ class ByzantinePSDataParallel(RobustDataParallel):
     _supports_sharding = False
 
     def __init__(self, model: nn.Module, loss_fn, ctx: DistContext, cfg: ByzPSConfig):
+        if cfg.worker_momentum:   # which gradients a server takes differs per step: no defined momentum
+            raise ValueError("worker_momentum is not supported by the Byzantine-PS engine (RobustDataParallel only)")
         top = ctx.world_size if cfg.ps_workers else ctx.world_size - 1   # someone must compute gradients
         if not (0 < cfg.num_ps <= top):
             raise ValueError(f"need 0 < num_ps <= {top} (world {ctx.world_size}, ps_workers={cfg.ps_workers}), "

@@ -112,6 +112,12 @@ class EngineConfig:
     dampening: float = 0.0
     weight_decay: float = 5e-4
     nesterov: bool = False
+    # worker-side momentum beta, 0 <= beta < 1 (docs/GAR_SEMANTICS.md "Worker momentum"): every logical
+    # worker sends m_i (m <- g on the first step, then beta * m + (1 - beta) * g) instead of its
+    # gradient, the condition under which centered clipping / NNM are robust to time-coupled attacks.
+    # Applied to the honest rows before the simulated attacks and the rule. 0: off (no state, no
+    # launch). Independent of the server momentum above; beta > 0 is normally run with momentum=0.
+    worker_momentum: float = 0.0
     exchange_dtype: torch.dtype = torch.bfloat16
     autocast_dtype: torch.dtype | None = torch.bfloat16
     byzantine: dict = field(default_factory=dict)   # global slot -> attack name
@@ -200,6 +206,8 @@ class RobustDataParallel:
         self.cfg = cfg
         self.device = ctx.device
         self._check_pre_aggregation()
+        if not 0.0 <= cfg.worker_momentum < 1.0:
+            raise ValueError(f"worker_momentum must satisfy 0 <= beta < 1, got {cfg.worker_momentum!r}")
         self.model = model.to(self.device)
         self._grouping = self._want_grouping(self.model)
         if (cfg.channels_last and self.device.type == "cuda") or self._grouping:
@@ -237,6 +245,9 @@ class RobustDataParallel:
         self.X = torch.zeros((self.k, 1 if self._sharded else self.world, self.ld), dtype=cfg.exchange_dtype,
                              device=self.device)
         self.G = None if self._sharded else self.X.view(self.n, self.ld)[:, : self.d]  # [n, d] GAR input
+        # worker-side momentum: one fp32 state row per local logical worker (local worker j: row j)
+        self.wmom = torch.zeros((self.k, self.ld), dtype=torch.float32, device=self.device) \
+            if cfg.worker_momentum > 0 else None
         # local slot order: honest workers first so colluders see their estimates
         self.local_slots = sorted(range(self.k), key=lambda j: (self.slot(j) in cfg.byzantine, j))
         self.step_count = 0
@@ -488,7 +499,7 @@ class RobustDataParallel:
                 # attacked from it (sharded: at exchange time, bucket by bucket)
                 self._write_row(self.X[j, self.xr, : self.d])
                 if self._shard is None:
-                    self._attack_rows(0, self.d, (j,))
+                    self._finish_rows(0, self.d, (j,))
                 works += issue.ready(j)
         for p in params:
             p.grad = None
@@ -1013,6 +1024,24 @@ class RobustDataParallel:
 
     _DEFAULT_GEN = object()
 
+    def _finish_rows(self, lo: int, hi: int, slots=None, gen=_DEFAULT_GEN) -> None:
+        """What happens to coordinates [lo, hi) of freshly written honest rows (``slots``: local worker
+        ids, default all) before they leave the rank: the worker-side momentum (every slot, Byzantine
+        ones included, from its honest gradient), then the simulated attacks, which so act on the
+        honest momenta. Elementwise, so a bucketed application equals the whole-row one bit for bit."""
+        beta = self.cfg.worker_momentum
+        hi = min(hi, self.d)
+        if beta > 0 and lo < hi:
+            from garfield_amd.ops import worker_momentum
+
+            first = self.step_count == 0
+            if slots is None:
+                worker_momentum.update(self.X[:, self.xr], self.wmom, beta, first, lo, hi)
+            else:
+                for j in slots:
+                    worker_momentum.update(self.X[j:j + 1, self.xr], self.wmom[j:j + 1], beta, first, lo, hi)
+        self._attack_rows(lo, hi, slots, gen)
+
     def _attack_rows(self, lo: int, hi: int, slots=None, gen=_DEFAULT_GEN) -> None:
         """Simulated Byzantine workers of this rank (``slots``: local worker ids, default
         all), on coordinates [lo, hi) of their rows, which hold their honest gradient.
@@ -1031,8 +1060,8 @@ class RobustDataParallel:
             row.copy_(apply_attack(attack, row.float(), None, gen))
 
     def _attack_local_rows(self) -> None:
-        """Overwrite the simulated Byzantine workers' rows (after the honest rows exist)."""
-        self._attack_rows(0, self.d)
+        """Worker momentum, then the simulated Byzantine workers' rows (after the honest rows exist)."""
+        self._finish_rows(0, self.d)
 
     def _collude(self, rows, slots=None) -> None:
         """The colluding attacks (lie, empire) on exchanged rows: ``rows[i]`` is (a
@@ -1128,7 +1157,7 @@ class RobustDataParallel:
         loss_out.copy_(loss.detach().float())
         self._write_row(self.X[j, self.xr, : self.d])
         if self._shard is None:
-            self._attack_rows(0, self.d, (j,), gen=None)   # captured: deterministic attacks only
+            self._finish_rows(0, self.d, (j,), gen=None)   # captured: deterministic attacks only
         for p in self.work_params:
             p.grad = None
 
@@ -1154,9 +1183,12 @@ class RobustDataParallel:
             # warm-up ON THE CAPTURE STREAM (lazy per-stream library state: BLAS / MIOpen
             # workspaces, algorithm caches) before any capture
             with torch.cuda.stream(s):
+                wmom = None if self.wmom is None else self.wmom.clone()
                 for j in self.local_slots:
                     x, y = self._static[j]
                     self._worker_body(j, x, y, self._static_loss[j])
+                if wmom is not None:   # the warm-up pass must not count as a step of the worker momenta
+                    self.wmom.copy_(wmom)
             s.synchronize()
             for j in self.local_slots:
                 g = torch.cuda.CUDAGraph()

@@ -59,6 +59,8 @@ class QuorumDataParallel(RobustDataParallel):
     _supports_sharding = False
 
     def __init__(self, model: nn.Module, loss_fn, ctx: DistContext, cfg: QuorumConfig):
+        if cfg.worker_momentum:   # a straggler that skips steps has no defined momentum
+            raise ValueError("worker_momentum is not supported by the quorum engine (RobustDataParallel only)")
         if not ctx.is_distributed:
             raise ValueError("the quorum engine needs an initialised process group")
         q = ctx.world_size if cfg.quorum is None else int(cfg.quorum)

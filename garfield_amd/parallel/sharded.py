@@ -282,7 +282,7 @@ class ShardedAggregator:
             else:
                 ctx = _nullctx()
             with ctx:
-                e._attack_rows(b.lo, b.hi)
+                e._finish_rows(b.lo, b.hi)
                 b.works = []
                 if self._coll and self._rccl is not None:   # straight from the exchange rows
                     self._rccl.exchange(*b.p2p, self._comm_stream)

@@ -10,6 +10,9 @@ in registration order (``server.py:196-200,289-297``). A checkpoint here holds:
 * ``momentum``: the engine's momentum in the same reference layout as ``flat``
   (so a channels_last / grouped GPU checkpoint resumes correctly on an NCHW
   engine, and vice versa), when present;
+* ``worker_momentum`` (engines with ``worker_momentum > 0``): the worker momenta of the whole job,
+  [n, d] fp32 in global slot order, each row in the reference layout, and ``worker_momentum_beta``;
+  a checkpoint without the key loads with zero state;
 * ``step`` and free-form ``meta``;
 * ``tuning`` (engine checkpoints): the measured kernel choices of the grouped step
   (``ops/tuning.py``), restored on load so the resumed run replays the same kernels.
@@ -37,8 +40,10 @@ def model_state(model: nn.Module, flat: torch.Tensor | None = None) -> dict:
 
 
 def save(path: str, model: nn.Module, step: int = 0, momentum: torch.Tensor | None = None,
-         meta: dict | None = None, flat: torch.Tensor | None = None, tuning: dict | None = None) -> str:
+         meta: dict | None = None, flat: torch.Tensor | None = None, tuning: dict | None = None,
+         extra: dict | None = None) -> str:
     state = model_state(model, flat)
+    state.update(extra or {})   # further engine state (tensors and primitives), e.g. the worker momenta
     state["step"] = int(step)
     if tuning:
         state["tuning"] = tuning
@@ -82,12 +87,33 @@ def save_engine(path: str, engine, meta: dict | None = None, write: bool = True)
         engine.sync_master()
     mom = engine.momentum_vector() if hasattr(engine, "momentum_vector") else engine.mom
     mom_ref = engine.flat.to_reference(mom)
+    wmom = worker_momentum_rows(engine)
     if not write:
         return path
     from garfield_amd.ops import tuning
 
+    extra = None if wmom is None else {"worker_momentum": wmom.cpu(), "worker_momentum_beta": float(engine.cfg.worker_momentum)}
     return save(path, engine.model, engine.step_count, mom_ref, meta, flat=engine.flat.reference_vector(),
-                tuning=tuning.export())
+                tuning=tuning.export(), extra=extra)
+
+
+def worker_momentum_rows(engine):
+    """The worker momenta of the whole job as [n, d] fp32 in global slot order (slot j * world + rank is
+    local worker j of ``rank``), each row in the reference layout; None without worker momentum.
+    Collective in multi-rank runs (the ranks' rows are all-gathered, as the momentum shards are)."""
+    wm = getattr(engine, "wmom", None)
+    if wm is None:
+        return None
+    if hasattr(engine, "synchronize"):
+        engine.synchronize()   # the sharded step updates the state on its exchange stream
+    rows = torch.stack([engine.flat.to_reference(wm[j]) for j in range(engine.k)])   # [k, d]
+    if engine.world > 1:
+        import torch.distributed as dist
+
+        out = torch.empty((engine.world, *rows.shape), dtype=rows.dtype, device=rows.device)
+        dist.all_gather_into_tensor(out.view(-1), rows.contiguous().view(-1))
+        rows = out.transpose(0, 1)   # [k, world, d]: slot order
+    return rows.reshape(engine.n, -1)
 
 
 def load_engine(path: str, engine) -> dict:
@@ -125,6 +151,19 @@ def load_engine(path: str, engine) -> dict:
             engine.mom.copy_(full[shard.sl])
         else:
             engine.mom.copy_(full[: engine.mom.numel()])
+    wm = getattr(engine, "wmom", None)
+    if wm is not None:
+        # this rank's k rows of the [n, d] worker momenta. A checkpoint without them (written with
+        # worker_momentum=0) resumes from zero state; `first` follows the restored step count, so the
+        # first resumed step then gives m = (1 - beta) * g.
+        wm.zero_()
+        saved = state.get("worker_momentum")
+        if saved is not None:
+            if tuple(saved.shape) != (engine.n, engine.flat.d):
+                raise ValueError(f"checkpoint holds worker momenta of shape {tuple(saved.shape)}, this engine has "
+                                 f"{engine.n} workers of {engine.flat.d} parameters")
+            for j in range(engine.k):
+                engine.flat.from_reference(saved[engine.slot(j)].to(wm.device), wm[j])
     engine.step_count = int(state.get("step", 0))
     # re-capture against the restored state: the per-worker graphs and the grouped graph
     # (whose replays read the master / working weights and the BatchNorm buffers in place,

@@ -2,13 +2,17 @@
 rule (new, absent from the reference): every gradient is replaced by the mean of its ``n - f``
 nearest gradients, itself included, then Krum, the geometric median, centered clipping or the average
 runs on the mixed gradients. The mixing is folded into the rule's weights (``docs/GAR_SEMANTICS.md``
-"Nearest-neighbour mixing"): the aggregate is Σ_j w_j g_j over the ORIGINAL gradients."""
+"Nearest-neighbour mixing"): the aggregate is Σ_j w_j g_j over the ORIGINAL gradients. The coordinate-wise
+trimmed mean and median have no weights to fold into: they run per coordinate over the n set means, which
+are never stored ("Nearest-neighbour mixing before a coordinate-wise rule")."""
 from garfield_amd.aggregators import register
 from garfield_amd.aggregators._common import n_of
 from garfield_amd.aggregators.average import check as _average_check
 from garfield_amd.aggregators.cclip import check as _cclip_check
 from garfield_amd.aggregators.geomed import check as _geomed_check
 from garfield_amd.aggregators.krum import check as _krum_check
+from garfield_amd.aggregators.median import check as _median_check
+from garfield_amd.aggregators.trimmed_mean import check as _trimmed_mean_check
 from garfield_amd.ops import gar
 
 
@@ -48,7 +52,27 @@ def _make(rule, own_check):
     register("nnm-" + rule, aggregate, check, influence=influence)
 
 
+def _make_coord(rule, own_check):
+    """NNM before a coordinate-wise rule: no weights to fold, the rule runs per coordinate over the n
+    set means (``gar.nnm_coord``); one ``f`` serves the mixing and the trimming."""
+    def aggregate(gradients, f=0, **kwargs):
+        return gar.nnm_coord(gradients, f, rule)
+
+    aggregate.__doc__ = f"Coordinate-wise {rule} of the gradients mixed over their n - f nearest."
+
+    def check(gradients, f=0, **kwargs):
+        msg = own_check(gradients=gradients, f=f, **kwargs)
+        if msg:
+            return msg
+        return _check_mix(gradients, f)
+
+    # as for the plain coordinate-wise rules there is no weight vector: no influence; no bound is claimed
+    register("nnm-" + rule, aggregate, check)
+
+
 _make("krum", _krum_check)
 _make("geomed", _geomed_check)
 _make("cclip", _cclip_check)
 _make("average", _average_check)
+_make_coord("trimmed-mean", _trimmed_mean_check)
+_make_coord("median", _median_check)

@@ -23,13 +23,15 @@ import torch
 from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
-         "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average", "cclip", "cclip-krum", "nnm-cclip"]
+         "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average", "cclip", "cclip-krum", "nnm-cclip",
+         "nnm-trimmed-mean", "nnm-median"]
 # "cclip-krum": centered clipping from the Multi-Krum start (start="krum"), Krum's f
 
 
 def default_f(rule: str, n: int) -> int | None:
-    if rule.startswith("nnm-"):   # the f of the plain rule (average: as geomed), so the pair is comparable
-        rule = "geomed" if rule == "nnm-average" else rule[4:]
+    if rule.startswith("nnm-"):   # the f of the plain rule (average: as geomed, median: as the trimmed mean:
+        # the plain median takes no f, the mixing needs one), so the pair is comparable
+        rule = {"nnm-average": "geomed", "nnm-median": "trimmed-mean"}.get(rule, rule[4:])
     if rule == "cclip-krum":
         rule = "krum"
     if rule in ("average", "average-nan", "median"):
@@ -128,7 +130,8 @@ def main(argv=None):
             inp = [G[i].clone() for i in range(n)] if a.list_input else G
             for rule in a.rules:
                 f = default_f(rule, n)
-                if rule in ("krum", "nnm-krum", "cclip-krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense") and f is None:
+                if rule in ("krum", "nnm-krum", "cclip-krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense",
+                            "nnm-trimmed-mean", "nnm-median") and f is None:
                     continue
                 if rule == "brute" and n > 20:
                     continue

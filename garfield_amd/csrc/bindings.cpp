@@ -237,6 +237,32 @@ void g_coordwise(const RowSet& rs, int mode, int f, int beta, const c10::optiona
                            garfield::bernoulli_threshold(p), out.data_ptr(), dtype_code(out), stream_of(rs.device));
 }
 
+int nnm_coord_mode(const std::string& mode, const char* who) {
+  if (mode == "trimmed-mean") return garfield::kTrimmedMean;
+  TORCH_CHECK(mode == "median", who, ": mode must be 'trimmed-mean' or 'median', got '", mode, "'");
+  return garfield::kMedian;
+}
+
+void g_nnm_coord(const RowSet& rs, const at::Tensor& masks, int n, int f, const std::string& mode, const at::Tensor& out) {
+  check_gpu(rs);
+  c10::hip::HIPGuard guard(rs.device.index());
+  const int code = nnm_coord_mode(mode, "gpu_nnm_coord");
+  TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_nnm_coord: 1 <= n <= ", garfield::kMaxRows);
+  TORCH_CHECK(n == rs.n, "gpu_nnm_coord: n = ", n, " but ", rs.n, " rows given");
+  TORCH_CHECK(f >= 0 && f < n, "gpu_nnm_coord: 0 <= f < n");
+  TORCH_CHECK(code != garfield::kTrimmedMean || n >= 2 * f + 1, "gpu_nnm_coord: the trimmed mean needs n >= 2f + 1");
+  TORCH_CHECK(masks.is_cuda() && out.is_cuda() && masks.device() == rs.device && out.device() == rs.device,
+              "gpu_nnm_coord: GPU tensors on the rows' device expected");
+  TORCH_CHECK(masks.scalar_type() == at::kLong && masks.is_contiguous() && masks.numel() == 2 * static_cast<int64_t>(n),
+              "gpu_nnm_coord: masks must be contiguous int64 of 2n entries");
+  TORCH_CHECK(out.is_contiguous() && out.numel() >= rs.d, "gpu_nnm_coord: out must be contiguous with at least d elements");
+  TORCH_CHECK(out.scalar_type() == at::kFloat || out.scalar_type() == rs.st,
+              "gpu_nnm_coord: out must be fp32 or of the rows' dtype");
+  garfield::gpu::nnm_coord(rs.table, rs.n, rs.d, rs.dt, code, f,
+                           reinterpret_cast<const unsigned long long*>(masks.data_ptr<int64_t>()), out.data_ptr(),
+                           dtype_code(out), stream_of(rs.device));
+}
+
 void g_sqdist(const RowSet& rs, const at::Tensor& center, const at::Tensor& slabs) {
   check_gpu(rs);
   c10::hip::HIPGuard guard(rs.device.index());
@@ -306,6 +332,25 @@ at::Tensor c_coordwise(const RowSet& rs, int mode, int f, int beta, const c10::o
     using T = decltype(z);
     garfield::cpu::coordwise<T>(r, mode, static_cast<size_t>(f), static_cast<size_t>(beta), w,
                                 static_cast<size_t>(t), seed, garfield::bernoulli_threshold(p), out.data_ptr<T>());
+    return 0;
+  });
+  return out;
+}
+
+at::Tensor c_mixed_coordwise(const RowSet& rs, const at::Tensor& masks, int c, const std::string& mode, int f) {
+  const int code = nnm_coord_mode(mode, "cpu_mixed_coordwise");
+  const int64_t n = rs.n;
+  TORCH_CHECK(c >= 1 && c <= n, "cpu_mixed_coordwise: 1 <= c <= n");
+  TORCH_CHECK(f >= 0 && f < n, "cpu_mixed_coordwise: 0 <= f < n");
+  TORCH_CHECK(code != garfield::kTrimmedMean || n >= 2 * f + 1, "cpu_mixed_coordwise: the trimmed mean needs n >= 2f + 1");
+  TORCH_CHECK(masks.scalar_type() == at::kLong && masks.numel() == 2 * n, "cpu_mixed_coordwise: masks must be [n, 2] int64");
+  auto mc = masks.contiguous().cpu();
+  std::vector<uint64_t> mk(2 * n);
+  for (int64_t e = 0; e < 2 * n; ++e) mk[e] = static_cast<uint64_t>(mc.data_ptr<int64_t>()[e]);
+  auto out = at::empty({rs.d}, at::TensorOptions().dtype(rs.st));
+  cpu_dispatch(rs, [&](auto r, auto z) {
+    using T = decltype(z);
+    garfield::cpu::mixed_coordwise<T>(r, mk, static_cast<size_t>(c), code, static_cast<size_t>(f), out.data_ptr<T>());
     return 0;
   });
   return out;
@@ -2061,6 +2106,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                              fptr(w), stream_of(a.device()), batch);
   }, py::arg("a"), py::arg("masks"), py::arg("n"), py::arg("f"), py::arg("w"), py::arg("batch") = 1,
      "Fold weights a [n] over the mixed rows back onto the original rows: w_j = sum of a_i over the sets holding j, / (n - f)");
+  m.def("gpu_nnm_sets", [](const at::Tensor& gram, int n, int f, const at::Tensor& masks, int batch) {
+    c10::hip::HIPGuard guard(gram.device().index());
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_nnm_sets: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(f >= 0 && f < n, "gpu_nnm_sets: 0 <= f < n");
+    TORCH_CHECK(batch >= 1, "batch must be >= 1");
+    TORCH_CHECK(gram.is_cuda() && masks.is_cuda(), "gpu_nnm_sets: GPU tensors expected");
+    TORCH_CHECK(masks.scalar_type() == at::kLong && masks.is_contiguous(), "gpu_nnm_sets: masks must be contiguous int64");
+    const int np = garfield::gpu::gram_padded(n);
+    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && masks.numel() >= static_cast<int64_t>(batch) * 2 * n,
+                "gpu_nnm_sets: buffers too small for the batch");
+    garfield::gpu::nnm_sets(fptr(gram), np, n, f, reinterpret_cast<unsigned long long*>(masks.data_ptr<int64_t>()),
+                            stream_of(gram.device()), batch);
+  }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("masks"), py::arg("batch") = 1,
+     "The neighbour sets of gpu_nnm_mix alone: masks [n, 2] int64 from the Gram, without the pseudo-Gram; batch > 1: "
+     "gram [batch, np, np] -> masks [batch, n, 2]");
+  def_rows(m, "gpu_nnm_coord",
+           [](const at::Tensor& G, const at::Tensor& masks, int n, int f, const std::string& mode, const at::Tensor& o) {
+             g_nnm_coord(rows_from_2d(G, true), masks, n, f, mode, o);
+           },
+           [](const std::vector<at::Tensor>& L, const at::Tensor& masks, int n, int f, const std::string& mode,
+              const at::Tensor& o) { g_nnm_coord(rows_from_list(L, true), masks, n, f, mode, o); },
+           "NNM before a coordinate-wise rule: out[x] = mode ('trimmed-mean' with f / 'median') over the n means of the "
+           "rows in each set of masks [n, 2], per coordinate; the mixed rows are never stored. args (rows, masks, n, f, "
+           "mode, out); out fp32 or the rows' dtype");
   def_rows(m, "gpu_lw_gram",
            [](const at::Tensor& G, const at::Tensor& jobs, const at::Tensor& seg_lo, const at::Tensor& slabs,
               const at::Tensor& gram) { g_lw_gram(rows_from_2d(G, true), jobs, seg_lo, slabs, gram); },
@@ -2755,6 +2824,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return weights_tensor(garfield::cpu::nnm_unmix(floats_from(a), mk, n, c), {n});
   }, py::arg("a"), py::arg("masks"), py::arg("c"),
      "Fold weights over the mixed rows back onto the original rows (fp32 [n])");
+  def_rows(m, "cpu_mixed_coordwise",
+           [](const at::Tensor& G, const at::Tensor& masks, int c, const std::string& mode, int f) {
+             return c_mixed_coordwise(rows_from_2d(G, false), masks, c, mode, f);
+           },
+           [](const std::vector<at::Tensor>& L, const at::Tensor& masks, int c, const std::string& mode, int f) {
+             return c_mixed_coordwise(rows_from_list(L, false), masks, c, mode, f);
+           },
+           "NNM before a coordinate-wise rule on the CPU: mode ('trimmed-mean' with f / 'median') over the means of the "
+           "rows in each set of masks [n, 2] (of c members), per coordinate; args (rows, masks, c, mode, f)");
   m.def("cpu_worker_momentum", [](const at::Tensor& X, const at::Tensor& M, int64_t lo, int64_t hi, double beta,
                                   bool first) {
     const int dt = check_worker_momentum(X, M, lo, hi, beta, false);

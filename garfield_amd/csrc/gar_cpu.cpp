@@ -216,7 +216,7 @@ std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t 
 
 // Nearest-neighbour mixing (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing"): the oracle's sums in
 // the oracle's order (set members ascending, the inner sum over l first).
-std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, std::vector<uint64_t>* masks) {
+std::vector<uint64_t> nnm_sets(const std::vector<double>& D, size_t n, size_t f) {
   const size_t c = n - f;
   const double inf = std::numeric_limits<double>::infinity();
   auto d0 = [&](size_t k, size_t l) {
@@ -224,7 +224,6 @@ std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, st
     return k == l ? 0.0 : (std::isfinite(v) ? v : inf);
   };
   std::vector<uint64_t> mk(2 * n, 0);
-  auto has = [&](size_t i, size_t j) { return (mk[2 * i + (j >> 6)] >> (j & 63)) & 1u; };
   for (size_t i = 0; i < n; ++i) {
     mk[2 * i + (i >> 6)] |= uint64_t{1} << (i & 63);
     for (size_t j = 0; j < n; ++j) {
@@ -239,6 +238,18 @@ std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, st
       if (rank + 1 < c) mk[2 * i + (j >> 6)] |= uint64_t{1} << (j & 63);
     }
   }
+  return mk;
+}
+
+std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, std::vector<uint64_t>* masks) {
+  const size_t c = n - f;
+  const double inf = std::numeric_limits<double>::infinity();
+  auto d0 = [&](size_t k, size_t l) {
+    const double v = D[k * n + l];
+    return k == l ? 0.0 : (std::isfinite(v) ? v : inf);
+  };
+  std::vector<uint64_t> mk = nnm_sets(D, n, f);
+  auto has = [&](size_t i, size_t j) { return (mk[2 * i + (j >> 6)] >> (j & 63)) & 1u; };
   std::vector<double> R(n * n, 0.0);   // R[j * n + k] = Σ_{l∈S_j} D⁰_kl
   for (size_t j = 0; j < n; ++j)
     for (size_t k = 0; k < n; ++k) {
@@ -475,6 +486,51 @@ void coordwise(const Rows<T>& r, int mode, size_t f, size_t beta, const std::vec
   });
 }
 
+// NNM before a coordinate-wise rule: per coordinate, the n set means (fp64 sums over the members in
+// ascending index, then / c) and coordwise()'s trimmed mean / median over them. Nothing depends on
+// where a coordinate sits in a chunk: any column split of the rows gives the same bits.
+template <class T>
+void mixed_coordwise(const Rows<T>& r, const std::vector<uint64_t>& masks, size_t c, int mode, size_t f, T* out) {
+  const size_t n = r.n;
+  if (mode != kTrimmedMean && mode != kMedian) throw std::invalid_argument("mixed_coordwise: trimmed mean or median");
+  std::vector<std::vector<size_t>> sets(n);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < n; ++j)
+      if ((masks[2 * i + (j >> 6)] >> (j & 63)) & 1u) sets[i].push_back(j);
+  const double cd = static_cast<double>(c);
+  parallel_for(0, r.d, default_chunks(r.d, 1024), [&](size_t, size_t lo, size_t hi) {
+    std::vector<double> g(n), v(n);
+    for (size_t x = lo; x < hi; ++x) {
+      for (size_t j = 0; j < n; ++j) g[j] = static_cast<double>(r.p[j][x]);
+      double res = 0.0;
+      if (mode == kMedian) {
+        size_t cnt = 0;
+        for (size_t i = 0; i < n; ++i) {
+          double s = 0.0;
+          for (size_t j : sets[i]) s += g[j];
+          s /= cd;
+          if (std::isfinite(s)) v[cnt++] = s;
+        }
+        if (cnt) {
+          std::nth_element(v.begin(), v.begin() + static_cast<long>(cnt / 2), v.begin() + static_cast<long>(cnt));
+          res = v[cnt / 2];
+        }
+      } else {
+        for (size_t i = 0; i < n; ++i) {
+          double s = 0.0;
+          for (size_t j : sets[i]) s += g[j];
+          v[i] = nan_to_inf(s / cd);
+        }
+        std::sort(v.begin(), v.end());
+        double s = 0.0;
+        for (size_t i = f; i < n - f; ++i) s += v[i];
+        res = s / static_cast<double>(n - 2 * f);
+      }
+      out[x] = static_cast<T>(res);
+    }
+  });
+}
+
 template <class T>
 std::vector<double> sqdist_to(const Rows<T>& r, const T* center) {
   const size_t n = r.n;
@@ -585,6 +641,7 @@ void worker_momentum(void* X, int dt, int64_t xstride, float* M, int64_t ld, siz
   template void combine<T>(const Rows<T>&, const std::vector<float>&, T*);                               \
   template void coordwise<T>(const Rows<T>&, int, size_t, size_t, const std::vector<float>&, size_t,     \
                              uint64_t, uint64_t, T*);                                                    \
+  template void mixed_coordwise<T>(const Rows<T>&, const std::vector<uint64_t>&, size_t, int, size_t, T*); \
   template std::vector<double> sqdist_to<T>(const Rows<T>&, const T*);
 
 GARFIELD_INSTANTIATE(float)

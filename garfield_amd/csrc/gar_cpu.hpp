@@ -47,6 +47,13 @@ std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t 
 std::vector<double> nnm_mix(const std::vector<double>& D, size_t n, size_t f, std::vector<uint64_t>* masks);
 std::vector<float> nnm_unmix(const std::vector<float>& a, const std::vector<uint64_t>& masks, size_t n, size_t c);
 
+// nnm_sets: the masks of nnm_mix alone. mixed_coordwise: NNM before a coordinate-wise rule, out[x] =
+// the rule (mode kTrimmedMean with f, or kMedian) over the n set means (1/c) Σ_{j∈S_i} row_j[x] of the
+// sets in `masks` (fp64 sums, members ascending); the mixed rows are never stored.
+std::vector<uint64_t> nnm_sets(const std::vector<double>& D, size_t n, size_t f);
+template <class T>
+void mixed_coordwise(const Rows<T>& r, const std::vector<uint64_t>& masks, size_t c, int mode, size_t f, T* out);
+
 // out = Σ_j w[j] g_j (accumulated in double)
 template <class T> void combine(const Rows<T>& r, const std::vector<float>& w, T* out);
 

@@ -215,6 +215,42 @@ __device__ __forceinline__ void fill_distances(const float* __restrict__ gram, i
   }
 }
 
+// The neighbour sets of nearest-neighbour mixing from the distances D of fill_distances (diagonal 0) by
+// the whole workgroup: S_i = row i, then the c - 1 nearest others by (distance, index), as ranks
+// counted by one lane per column and a ballot. Row i is wave i % (waves)'s; a set is two 64-bit mask
+// words, written to `masks` and (when given) to the LDS copy Mk. Shared by k_nnm_mix and k_nnm_sets.
+__device__ __forceinline__ void nnm_build_sets(const float* D, int n, int c, unsigned long long* Mk,
+                                               unsigned long long* __restrict__ masks) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
+  const int pitch = n + 1;
+  for (int i = wave; i < n; i += nwaves) {
+    const float* row = D + i * pitch;
+#pragma unroll
+    for (int cc = 0; cc < 2; ++cc) {
+      const int j = lane + 64 * cc;
+      bool member = false;
+      if (j < n) {
+        if (j == i) {
+          member = true;
+        } else {
+          const float dj = row[j];
+          int rank = 0;
+          for (int k = 0; k < n; ++k) {
+            const float dk = row[k];
+            rank += (k != i) && (dk < dj || (dk == dj && k < j));
+          }
+          member = rank < c - 1;
+        }
+      }
+      const unsigned long long b = __ballot(member);
+      if (lane == 0) {
+        if (Mk) Mk[2 * i + cc] = b;
+        masks[2 * i + cc] = b;
+      }
+    }
+  }
+}
+
 __device__ __forceinline__ int score_rank(const float* s, int n, int i) {
   const float si = sanitize_inf(s[i]);
   int rank = 0;

@@ -53,6 +53,14 @@ void nnm_mix(const float* gram, int np, int n, int f, float* H, unsigned long lo
 void nnm_unmix(const float* a, const unsigned long long* masks, int n, int f, float* w, hipStream_t stream,
                int batch = 1);
 
+// NNM before a coordinate-wise rule (gar_nnm_coord.hip). nnm_sets: masks[n][2] alone, nnm_mix's sets bit
+// for bit without its pseudo-Gram; batch as krum_select. nnm_coord: out[x] = the rule (mode kTrimmedMean
+// with f, n >= 2f + 1, or kMedian) over the n mixed values (1/c) Σ_{j∈S_i} row_j[x], c = n - f, of every
+// coordinate, never stored; n <= kMaxRows, dt f32 / bf16 / f16, out fp32 or the rows' dtype.
+void nnm_sets(const float* gram, int np, int n, int f, unsigned long long* masks, hipStream_t stream, int batch = 1);
+void nnm_coord(const RowTable& rows, int n, int64_t d, int dt, int mode, int f, const unsigned long long* masks,
+               void* out, int out_dt, hipStream_t stream);
+
 // W[t][n]: row k = uniform weights of the (m-k) best-scoring gradients at step k
 // batch > 1: gram [batch][np][np] -> W [batch][t][n]
 void bulyan_select(const float* gram, int np, int n, int f, int m, int t, float* W,

@@ -68,38 +68,11 @@ __global__ __launch_bounds__(1024) void k_nnm_mix(const float* __restrict__ gram
   double* Md = lds64 + n * kJB;                       // n   M_ii (+inf: row i is tainted)
   u64* Mk = reinterpret_cast<u64*>(Md + n);           // 2n  the sets
   float* D = reinterpret_cast<float*>(Mk + 2 * n);    // n * (n + 1), diagonal 0
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int pitch = n + 1;
 
   fill_distances(gram, np, n, D, 0.f);
   __syncthreads();
   // S_i: row i first, then the c - 1 nearest others by (distance, index); ranks are counted
-  for (int i = wave; i < n; i += 16) {
-    const float* row = D + i * pitch;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const int j = lane + 64 * cc;
-      bool member = false;
-      if (j < n) {
-        if (j == i) {
-          member = true;
-        } else {
-          const float dj = row[j];
-          int rank = 0;
-          for (int k = 0; k < n; ++k) {
-            const float dk = row[k];
-            rank += (k != i) && (dk < dj || (dk == dj && k < j));
-          }
-          member = rank < c - 1;
-        }
-      }
-      const u64 b = __ballot(member);
-      if (lane == 0) {
-        Mk[2 * i + cc] = b;
-        masks[2 * i + cc] = b;
-      }
-    }
-  }
+  nnm_build_sets(D, n, c, Mk, masks);
   __syncthreads();
   // the M_ii first: R for kJB columns at a time, the fp64 n x n matrix does not fit next to D
   for (int j0 = 0; j0 < n; j0 += kJB) {

@@ -718,6 +718,99 @@ def nnm(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
     return _combine_rows(rows, _nnm_w(rows, f, rule, **kw))
 
 
+# NNM before a coordinate-wise rule (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing before a
+# coordinate-wise rule"): there is no weight vector to fold the mixing into, so per coordinate the n set
+# means are formed and the rule runs over them, in one pass over the rows; the mixed rows are never stored.
+
+NNM_COORD_RULES = ("trimmed-mean", "median")
+
+
+def _nnm_coord_args(n: int, f: int, rule: str) -> None:
+    if rule not in NNM_COORD_RULES:
+        raise ValueError(f"nnm: unsupported coordinate-wise rule {rule!r}; available: {NNM_COORD_RULES}")
+    if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < n:
+        raise ValueError(f"nnm: expected 0 <= f < n, got f = {f!r}, n = {n}")
+    if rule == "trimmed-mean" and n < 2 * f + 1:
+        raise ValueError(f"nnm-trimmed-mean: expected n >= 2f + 1, got n = {n}, f = {f}")
+
+
+def nnm_coord_into(C, ws: Workspace, G, g: torch.Tensor, n: int, f: int, rule: str, out: torch.Tensor) -> None:
+    """``out`` (fp32 or the rows' dtype, >= d elements) = ``rule`` over the rows ``G`` mixed over their
+    n - f nearest, from a device Gram ``g`` (pitch gram_padded(n), n <= MAX_ROWS): the sets launch, then
+    k_nnm_coord. Every buffer comes from ``ws`` (capture-safe)."""
+    masks = ws.get("nnm_masks", 2 * n, torch.int64)
+    C.gpu_nnm_sets(g, n, f, masks)
+    C.gpu_nnm_coord(G, masks, n, f, rule, out)
+
+
+def nnm_coord_from_distances(C, X: torch.Tensor, D: torch.Tensor, f: int, rule: str) -> torch.Tensor:
+    """``rule`` over the CPU rows ``X`` [n, d'] mixed by the sets of the squared distances ``D`` (which
+    may come from more coordinates than X holds: a shard of the rows with the distances summed over
+    ranks). The C++ path for n <= MAX_ROWS, else the oracle. A coordinate's result does not depend on
+    which other coordinates X holds."""
+    n = X.shape[0]
+    if C is None or n > MAX_ROWS:
+        Y = ref.nnm_mixed_rows(X, ref.nnm_sets(D, f))
+        return (ref.trimmed_mean(Y, f) if rule == "trimmed-mean" else ref.median(Y)).to(X.dtype)
+    _, masks = C.cpu_nnm_mix(D, f)
+    return C.cpu_mixed_coordwise(X, masks, n - f, rule, f)
+
+
+def _large_nnm_coord(rows: Rows, f: int, rule: str) -> torch.Tensor:
+    """MAX_ROWS < n <= LARGE_ROWS on the GPU, as Bulyan's large case: the sets from the Gram, the mixed
+    rows V = (S / c) · X column chunk by chunk into a bounded fp32 buffer, the radix-select rule on each."""
+    n, c = rows.n, rows.n - f
+    X = _matrix(rows)
+    _, S = nnm_from_gram(_large_gram(rows), f)
+    Wd = (S.float() / float(c)).contiguous()
+    out = torch.empty(rows.d, dtype=torch.float32, device=rows.device)
+    step = max(1, (1 << 28) // (4 * n))
+    Vbuf = torch.empty((n, min(step, rows.d)), dtype=torch.float32, device=rows.device)
+    for c0 in range(0, rows.d, step):
+        w = min(step, rows.d - c0)
+        Xc = X[:, c0:c0 + w]
+        V = large_wx(Wd, Xc, Vbuf[:, :w])
+        bad = (~torch.isfinite(Xc)).any(0).nonzero().flatten()
+        if bad.numel():   # 0 * inf poisoned every set of these coordinates: plain sums over the members
+            Xb = Xc[:, bad].float()
+            V[:, bad] = torch.where(S[:, :, None], Xb[None], torch.zeros((), device=X.device)).sum(1) / float(c)
+        _native.native().gpu_large_coord(V, _LARGE_MODE[rule], f, 0, out[c0:c0 + w])
+    return out
+
+
+def nnm_coord(gradients, f: int, rule: str = "trimmed-mean") -> torch.Tensor:
+    """``rule`` ("trimmed-mean" with the same ``f``, or "median") over the rows mixed over their n - f
+    nearest, in the gradients' dtype. GPU, n <= MAX_ROWS: Gram -> sets -> k_nnm_coord, one pass over the
+    rows; CPU: the C++ path (the oracle without the extension); beyond MAX_ROWS the mixed rows go
+    through a bounded buffer (GPU) or torch (CPU)."""
+    rows = prepare(gradients)
+    n = rows.n
+    _nnm_coord_args(n, f, rule)
+    if _large(rows):
+        return _finish(_large_nnm_coord(rows, f, rule), rows)
+    if n > MAX_ROWS:
+        X = rows.stacked()
+        X = X.double() if X.dtype == torch.float64 else X.float()
+        _, S = nnm_from_gram(X.double() @ X.double().T, f)
+        zero = torch.zeros((), dtype=X.dtype, device=X.device)
+        step = max(1, (1 << 24) // (n * n))   # the [n, n, step] member tensor stays bounded
+        outs = []
+        for c0 in range(0, rows.d, step):
+            Y = torch.where(S[:, :, None], X[None, :, c0:c0 + step], zero).sum(1) / float(n - f)
+            outs.append(_torch_coord(Y, rule, f, 0, 0, 1.0))
+        return _finish(torch.cat(outs), rows)
+    C = _C_for(rows)
+    if rows.device.type == "cuda":
+        ws = workspace(rows)
+        out = torch.empty(rows.d, dtype=rows.dtype, device=rows.device)
+        nnm_coord_into(C, ws, rows.obj, _gram_into(C, rows, ws), n, f, rule, out)
+        return _finish(out, rows)
+    if C is None:
+        return ref.nnm_coord(rows.stacked(), f, rule).to(rows.out_dtype)
+    _, masks = C.cpu_nnm_mix(C.cpu_pairwise(rows.obj), f)
+    return _finish(C.cpu_mixed_coordwise(rows.obj, masks, n - f, rule, f), rows)   # rows.obj may be a list
+
+
 def bulyan_weights(gradients, f: int, m: int | None = None) -> torch.Tensor:
     rows = prepare(gradients)
     m = rows.n - f - 2 if m is None else m
@@ -1113,6 +1206,8 @@ RULES = {
     "nnm-krum": lambda gradients, f, m=None, **_: nnm(gradients, f, "krum", m=m),
     "nnm-geomed": lambda gradients, f=0, iters=32, nu=1e-6, **_: nnm(gradients, f, "geomed", iters=iters, nu=nu),
     "nnm-average": lambda gradients, f=0, **_: nnm(gradients, f, "average"),
+    "nnm-trimmed-mean": lambda gradients, f, **_: nnm_coord(gradients, f, "trimmed-mean"),
+    "nnm-median": lambda gradients, f=0, **_: nnm_coord(gradients, f, "median"),
     "condense": condense,
     "trimmed-mean": trimmed_mean,
     "averaged-median": averaged_median,

@@ -298,6 +298,33 @@ def nnm(G, f: int, rule: str = "krum", **kw) -> torch.Tensor:
     return combine(G, nnm_weights(pairwise_sqdist(G), f, rule, **kw).double())
 
 
+def nnm_mixed_rows(X, sets) -> torch.Tensor:
+    """The mixed rows [n, d] (fp64): y_i[x] = (1/c) Σ_{j∈S_i} x_j[x], plain IEEE sums over the members in
+    ascending index. A non-finite member makes exactly the mixed values of the sets that hold it
+    non-finite."""
+    X = _g(X)
+    out = torch.empty((len(sets), X.shape[1]), dtype=torch.float64)
+    for i, s in enumerate(sets):
+        acc = torch.zeros(X.shape[1], dtype=torch.float64)
+        for j in s:   # one fp64 addition per member and coordinate, members ascending
+            acc = acc + X[j]
+        out[i] = acc / len(s)
+    return out
+
+
+def nnm_coord(G, f: int, rule: str = "trimmed-mean") -> torch.Tensor:
+    """A coordinate-wise rule (trimmed-mean with the same f, or median) over the rows mixed over their
+    n - f nearest: pairwise_sqdist -> nnm_sets -> nnm_mixed_rows -> the plain rule."""
+    X = _g(G)
+    n = X.shape[0]
+    if rule not in ("trimmed-mean", "median"):
+        raise ValueError(f"nnm: unsupported coordinate-wise rule {rule!r} (trimmed-mean, median)")
+    if rule == "trimmed-mean" and n < 2 * f + 1:
+        raise ValueError(f"nnm-trimmed-mean: expected n >= 2f + 1, got n = {n}, f = {f}")
+    Y = nnm_mixed_rows(X, nnm_sets(pairwise_sqdist(X), f))
+    return trimmed_mean(Y, f) if rule == "trimmed-mean" else median(Y)
+
+
 def bulyan_weights(D: torch.Tensor, f: int, m: int | None = None) -> torch.Tensor:
     n = D.shape[0]
     m = n - f - 2 if m is None else m

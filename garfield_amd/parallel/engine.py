@@ -52,6 +52,9 @@ os.environ.setdefault("MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_WRW_XDLOPS", "0
 WEIGHTED_RULES = {"average", "krum", "brute", "aksel", "geomed", "cclip"}
 _LP_MODULES = (nn.modules.conv._ConvNd, nn.Linear)
 COORD_RULES = {"median", "trimmed-mean", "averaged-median", "average-nan", "condense", "bulyan"}
+# coordinate-wise rules accepted behind pre_aggregation="nnm" (gar.nnm_coord; "nnm-median" exists through
+# the functional interface and the registry only)
+NNM_ENGINE_COORD_RULES = ("trimmed-mean",)
 LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip"}   # per-layer != flat only for distance-based rules
 # Layer-wise Krum as device operations (gar_layerwise.hip: one segmented Gram launch, a batched
 # selection, one segmented combine + SGD); "0" runs the per-segment loop (the reference form).
@@ -103,8 +106,10 @@ class EngineConfig:
     # "nnm": nearest-neighbour mixing before the rule (every gradient replaced by the mean of its
     # n - f nearest, itself included; docs/GAR_SEMANTICS.md), folded into the rule's row weights, for
     # gar in {krum, geomed, cclip, average}: the flat step (GPU, CPU, n > 128), explicit row lists and the
-    # sharded flat selection. Not yet supported (ValueError at construction): any other rule,
-    # layerwise=True, and the sharded path with n > 128 rows on the GPU. None: exactly today's paths.
+    # sharded flat selection. gar="trimmed-mean" has no weights to fold into: the rule runs per coordinate
+    # over the n set means, which are never stored (gar.nnm_coord), on the same paths. Not yet supported
+    # (ValueError at construction): any other rule (median and bulyan included), layerwise=True, and the
+    # sharded path with n > 128 rows on the GPU. None: exactly today's paths.
     pre_aggregation: str | None = None
     workers_per_rank: int = 8
     lr: float = 0.1
@@ -432,9 +437,9 @@ class RobustDataParallel:
             return
         if cfg.pre_aggregation != "nnm":
             raise ValueError(f"unknown pre_aggregation {cfg.pre_aggregation!r}; available: 'nnm'")
-        if cfg.gar not in gar.NNM_RULES:
+        if cfg.gar not in gar.NNM_RULES + NNM_ENGINE_COORD_RULES:
             raise ValueError(f"pre_aggregation='nnm' is not yet supported with gar={cfg.gar!r}; "
-                             f"available: {gar.NNM_RULES}")
+                             f"available: {gar.NNM_RULES + NNM_ENGINE_COORD_RULES}")
         if cfg.layerwise:
             raise ValueError("pre_aggregation='nnm' is not yet supported with layerwise=True")
         if (self.device.type == "cuda" and cfg.workers_per_rank * self.ctx.world_size > gar.MAX_ROWS
@@ -561,7 +566,10 @@ class RobustDataParallel:
                 gkw["m"] = cfg.m
             if rule == "condense":
                 gkw.setdefault("seed", cfg.seed + self.step_count)
-            if rule in ("geomed", "cclip") or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
+            if cfg.pre_aggregation and rule in NNM_ENGINE_COORD_RULES:   # no weights: the rule over the set means
+                self.last_weights = None
+                g = gar.nnm_coord(self.G.float(), cfg.f, rule).float()
+            elif rule in ("geomed", "cclip") or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
                 self.last_weights = w = self._weights(rule, kw, self.G.float())
                 g = gar.combine(self.G.float(), w).float()
             else:
@@ -581,7 +589,7 @@ class RobustDataParallel:
             g = gar.combine(self.G, w)
         else:
             self.last_weights = None
-            g = gar.aggregate(rule, self.G, **self._rule_kwargs())
+            g = gar.aggregate(self._rule_name(), self.G, **self._rule_kwargs())
         self._C.gpu_combine_sgd([g.contiguous()], self._one, self.flat.data[: self.d], self.mom[: self.d], None,
                                 self._shadow, cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov,
                                 first)
@@ -732,7 +740,11 @@ class RobustDataParallel:
         modes = gar._MODE
         G = self.G if G is None else G
         n = len(G) if isinstance(G, (list, tuple)) else G.shape[0]
-        if rule == "bulyan":
+        if self.cfg.pre_aggregation:   # Gram -> sets -> k_nnm_coord: the rule over the n set means, never stored
+            rows = gar.prepare(G)
+            ws = gar.workspace(rows)
+            gar.nnm_coord_into(C, ws, rows.obj, gar._gram_into(C, rows, ws), n, f, rule, out)
+        elif rule == "bulyan":
             t = n - 2 * f - 2
             W = gar.bulyan_weights(G, f, self.cfg.m)
             C.gpu_coordwise(G, modes["bulyan-tail"], f, t - 2 * f, W.reshape(-1), t, 0, 1.0, out)
@@ -750,6 +762,11 @@ class RobustDataParallel:
                             float(kw.get("p", 0.9)), out)
         else:
             raise ValueError(rule)
+
+    def _rule_name(self) -> str:
+        """The rule's name in gar.RULES: a coordinate-wise rule behind the mixing is its "nnm-" entry."""
+        cfg = self.cfg
+        return ("nnm-" + cfg.gar) if cfg.pre_aggregation and cfg.gar in NNM_ENGINE_COORD_RULES else cfg.gar
 
     def _rule_kwargs(self) -> dict:
         cfg = self.cfg
@@ -795,18 +812,18 @@ class RobustDataParallel:
             if len(rows) <= gar.MAX_ROWS:   # fp32 aggregate, as the synchronous step's
                 self._coordinate(cfg.gar, dict(cfg.gar_kwargs), g, rows)
             else:
-                g.copy_(gar.aggregate(cfg.gar, rows, **self._rule_kwargs()))
+                g.copy_(gar.aggregate(self._rule_name(), rows, **self._rule_kwargs()))
             C.gpu_combine_sgd([g], self._one, param, mom, None, self._shadow, cfg.lr, cfg.momentum, cfg.dampening,
                               cfg.weight_decay, cfg.nesterov, first)
         else:
             # as a [rows, d] fp32 matrix: the aggregate keeps fp32 (a list of 16-bit rows
             # would round it to the rows' dtype), as the synchronous step's
             X = torch.stack([r.float() for r in rows])
-            if cfg.pre_aggregation or cfg.gar == "cclip":
+            if (cfg.pre_aggregation or cfg.gar == "cclip") and cfg.gar not in NNM_ENGINE_COORD_RULES:
                 self.last_weights = w = self._weights(cfg.gar, dict(cfg.gar_kwargs), X)
                 g = gar.combine(X, w).float()
             else:
-                g = gar.aggregate(cfg.gar, X, **self._rule_kwargs()).float()
+                g = gar.aggregate(self._rule_name(), X, **self._rule_kwargs()).float()
             self._sgd_cpu(g, first)
 
     def _sgd_cpu(self, g: torch.Tensor, first: bool) -> None:

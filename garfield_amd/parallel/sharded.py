@@ -549,6 +549,20 @@ class ShardedAggregator:
                 C.gpu_aksel_select(allslabs.contiguous().view(-1), n, c, w, dists)
             else:
                 total = self._sum_over_ranks(total)
+                if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:
+                    # the sets once from the summed Gram, identical on every rank; then per bucket the rule
+                    # over the n set means of the owned coordinates (never stored), as Bulyan's tail below
+                    masks = self._ws_any().get("nnm_masks", 2 * n, torch.int64)
+                    C.gpu_nnm_sets(total, n, f, masks)
+                    e.last_weights = None
+
+                    def mixed(b):
+                        g = self._gagg(b)
+                        C.gpu_nnm_coord(b.rows, masks, n, f, rule, g)
+                        p, mom, sh = self._param(b)
+                        C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
+                    self._update_buckets(mixed)
+                    return
                 w = self._select(C, total, rule, f, cfg)
             if rule != "bulyan":
                 e.last_weights = w
@@ -946,6 +960,9 @@ class ShardedAggregator:
                 return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
             D = self._sum_over_ranks(gar.pairwise_distances(X))
             m = cfg.m if cfg.m is not None else n - f - 2
+            if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:   # the same sets on every rank, no weights
+                e.last_weights = None
+                return gar.nnm_coord_from_distances(C, X, D, f, rule)
             if cfg.pre_aggregation:   # the mix runs on the summed distances: the same w on every rank
                 w = gar.nnm_weights_from_distances(C, D, f, rule, m, *e._geomed_args(kw), cclip=e._cclip_args(kw))
                 e.last_weights = w

@@ -155,6 +155,18 @@ class CClipGAR(_GAR):
         return kw
 
 
+class DnCGAR(_GAR):
+    """DnC spectral filtering (new, absent from the reference); ``m:<int>`` (0: n - f) and ``iters:<int>`` optional."""
+    rule_name = "dnc"
+    defaults = {"m": 0, "iters": 16}
+
+    def kwargs(self):
+        kw = {"iters": int(self.args["iters"])}
+        if self.args["m"]:
+            kw["m"] = int(self.args["m"])
+        return kw
+
+
 class NNMKrumGAR(KrumGAR):
     """Multi-Krum after nearest-neighbour mixing over the n - f nearest (new, absent from the reference)."""
     rule_name = "nnm-krum"
@@ -185,5 +197,6 @@ for _name, _cls in (("average", AverageGAR), ("average-nan", AverageNaNGAR), ("m
                     ("krum-tf", KrumGAR), ("bulyan", BulyanGAR), ("bulyan-py", BulyanGAR),
                     ("condense", CondenseGAR), ("trimmed-mean", TrimmedMeanGAR),
                     ("geomed", GeoMedGAR), ("nnm-krum", NNMKrumGAR), ("nnm-geomed", NNMGeoMedGAR),
-                    ("nnm-average", NNMAverageGAR), ("cclip", CClipGAR), ("nnm-cclip", NNMCClipGAR)):
+                    ("nnm-average", NNMAverageGAR), ("cclip", CClipGAR), ("nnm-cclip", NNMCClipGAR),
+                    ("dnc", DnCGAR)):
     register(_name, _cls)

@@ -42,7 +42,9 @@ def add_common(p: argparse.ArgumentParser, ps: bool = True) -> argparse.Argument
     p.add_argument("--opt_args", type=json.loads, default={"lr": "0.1"},
                    help='Optimizer arguments as JSON, e.g. \'{"lr":"0.1"}\'')
     p.add_argument("--num_iter", type=int, default=5000)
-    p.add_argument("--gar", type=str, default="average")
+    p.add_argument("--gar", type=str, default="average",
+                   help="GAR name (garfield_amd.aggregators.gars): average, median, krum, bulyan, brute, aksel, condense, "
+                        "trimmed-mean, averaged-median, average-nan, geomed, cclip, dnc (DnC spectral filtering), nnm-*")
     p.add_argument("--pre_aggregation", type=str, default=None, choices=["nnm"],
                    help="nnm: nearest-neighbour mixing before --gar (krum, geomed, cclip, average): every gradient is "
                         "replaced by the mean of its n - f nearest, for heterogeneous (--non_iid) data")

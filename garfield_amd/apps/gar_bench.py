@@ -24,7 +24,7 @@ from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
          "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average", "cclip", "cclip-krum", "nnm-cclip",
-         "nnm-trimmed-mean", "nnm-median"]
+         "nnm-trimmed-mean", "nnm-median", "dnc"]
 # "cclip-krum": centered clipping from the Multi-Krum start (start="krum"), Krum's f
 
 

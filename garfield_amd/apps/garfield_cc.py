@@ -70,7 +70,7 @@ def parse(argv=None):
                         "25,50 for resnet50, as the reference's MultiStepLR, trainer.py:273-274,290-291; none else)")
     p.add_argument("--lr_gamma", type=float, default=0.1)
     p.add_argument("--num_iter", type=int, default=0, help="stop after this many iterations (0: epochs)")
-    p.add_argument("--aggregator", default="vanilla", help="GAR name; vanilla = average (reference default)")
+    p.add_argument("--aggregator", default="vanilla", help="GAR name; vanilla = average (reference default); the new rules geomed, cclip and dnc included")
     p.add_argument("--pre_aggregation", default=None, choices=["nnm"],
                    help="nnm: nearest-neighbour mixing before --aggregator (krum, geomed, cclip, average)")
     p.add_argument("--mar", default="median")

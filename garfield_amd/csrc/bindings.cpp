@@ -2073,6 +2073,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "Centered-clipping weights (iters clipping rounds on the Gram's distances) on device; rows nw..n-1 are basis-only; "
      "a0 = the start weights (None: uniform on the workers; may be the weights buffer); tau <= 0: the radius from the "
      "data; dists = the centre's distance to every valid worker; batch > 1: gram [batch, np, np] -> weights / dists [batch, n]");
+  m.def("gpu_dnc_select", [](const at::Tensor& gram, int n, int mm, int iters, const at::Tensor& w,
+                             const at::Tensor& scores, int batch) {
+    c10::hip::HIPGuard guard(gram.device().index());
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_dnc_select: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(mm >= 1 && mm <= n && iters >= 1, "gpu_dnc_select: 1 <= m <= n and iters >= 1");
+    TORCH_CHECK(batch >= 1, "batch must be >= 1");
+    TORCH_CHECK(gram.is_cuda() && w.is_cuda() && scores.is_cuda(), "gpu_dnc_select: GPU tensors expected");
+    const int np = garfield::gpu::gram_padded(n);
+    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && w.numel() >= static_cast<int64_t>(batch) * n &&
+                    scores.numel() >= static_cast<int64_t>(batch) * n,
+                "gpu_dnc_select: buffers too small for the batch");
+    garfield::gpu::dnc_select(fptr(gram), np, n, mm, iters, fptr(w), fptr(scores), stream_of(gram.device()), batch);
+  }, py::arg("gram"), py::arg("n"), py::arg("m"), py::arg("iters"), py::arg("weights"), py::arg("scores"),
+     py::arg("batch") = 1,
+     "DnC spectral-filtering weights (power rounds on the doubly centred distances of the Gram) on device; scores = "
+     "the squared projection of every row on the top principal direction; batch > 1: gram [batch, np, np] -> "
+     "weights / scores [batch, n]");
   m.def("gpu_nnm_mix", [](const at::Tensor& gram, int n, int f, const at::Tensor& H, const at::Tensor& masks,
                           int batch) {
     c10::hip::HIPGuard guard(gram.device().index());
@@ -2799,6 +2816,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return weights_tensor(garfield::cpu::cclip_weights(dist_from(D), n, nw, start, tau, f, iters), {n});
   }, py::arg("D"), py::arg("nw"), py::arg("a0"), py::arg("tau"), py::arg("f"), py::arg("iters") = 3,
      "Centered-clipping weights from squared distances (fp32 [n]); a0 None: uniform on the workers; tau <= 0: from the data");
+  m.def("cpu_dnc_weights", [](const at::Tensor& D, int mm, int iters) {
+    TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_dnc_weights: D must be [n, n]");
+    const int64_t n = D.size(0);
+    TORCH_CHECK(mm >= 1 && mm <= n && iters >= 1, "cpu_dnc_weights: 1 <= m <= n and iters >= 1");
+    std::vector<float> scores;
+    auto w = garfield::cpu::dnc_weights(dist_from(D), n, mm, iters, &scores);
+    return py::make_tuple(weights_tensor(w, {n}), weights_tensor(scores, {n}));
+  }, py::arg("D"), py::arg("m"), py::arg("iters") = 16,
+     "DnC spectral-filtering weights and outlier scores from squared distances (fp32 [n] each)");
   m.def("cpu_nnm_mix", [](const at::Tensor& D, int f) {
     TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_nnm_mix: D must be [n, n]");
     const int64_t n = D.size(0);

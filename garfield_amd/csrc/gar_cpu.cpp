@@ -147,6 +147,86 @@ std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t
   return w;
 }
 
+// DnC spectral filtering on the distance matrix alone (docs/GAR_SEMANTICS.md "Spectral filtering"):
+// exactly `iters` power rounds on K = -½ J D J (never stored), every sum in index order over the
+// valid rows; the min(m, |V|) lowest fp32 scores are kept.
+std::vector<float> dnc_weights(const std::vector<double>& D, size_t n, size_t m, size_t iters,
+                               std::vector<float>* scores_out) {
+  std::vector<char> valid(n, 0);
+  size_t nv = 0;
+  for (size_t i = 0; i < n; ++i) {
+    for (size_t j = 0; j < n; ++j)
+      if (j != i && std::isfinite(D[i * n + j])) valid[i] = 1;
+    nv += valid[i];
+  }
+  if (nv == 0) {
+    if (scores_out) scores_out->assign(n, 0.f);
+    return std::vector<float>(n, static_cast<float>(1.0 / static_cast<double>(n)));
+  }
+  auto dist = [&](size_t i, size_t j) {
+    const double v = D[i * n + j];
+    return (i != j && std::isfinite(v)) ? v : 0.0;
+  };
+  const double nvd = static_cast<double>(nv);
+  const size_t kv = std::min(m, nv);
+  std::vector<double> r(n, 0.0), b(n, 0.0), u(n, 0.0), t(n, 0.0);
+  for (size_t i = 0; i < n; ++i) {
+    if (!valid[i]) continue;
+    double acc = 0.0;
+    for (size_t j = 0; j < n; ++j)
+      if (valid[j]) acc += dist(i, j);
+    r[i] = acc / nvd;
+  }
+  double g = 0.0;
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i]) g += r[i];
+  g /= nvd;
+  size_t star = n;   // the lowest valid index that attains max κ, κ_i = r_i - g/2
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i] && (star == n || r[i] - 0.5 * g > r[star] - 0.5 * g)) star = i;
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i]) b[i] = -0.5 * (dist(i, star) - r[i] - r[star] + g);
+  for (size_t it = 0; it < iters; ++it) {
+    double nu = 0.0;
+    for (size_t i = 0; i < n; ++i)
+      if (valid[i]) nu += b[i] * b[i];
+    nu = std::sqrt(nu);
+    double c = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+      if (!valid[i]) continue;
+      u[i] = nu > 0.0 ? b[i] / nu : 0.0;
+      c += u[i];
+    }
+    c /= nvd;
+    double tm = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+      if (!valid[i]) continue;
+      double acc = 0.0;
+      for (size_t j = 0; j < n; ++j)
+        if (valid[j]) acc += dist(i, j) * (u[j] - c);
+      t[i] = acc;
+      tm += acc;
+    }
+    tm /= nvd;
+    for (size_t i = 0; i < n; ++i)
+      if (valid[i]) b[i] = -0.5 * (t[i] - tm);
+  }
+  double lam = 0.0;
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i]) lam += u[i] * b[i];
+  std::vector<float> s(n, static_cast<float>(kInf));
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i]) s[i] = lam > 0.0 ? static_cast<float>(b[i] * b[i] / lam) : 0.f;
+  std::vector<size_t> order;
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i]) order.push_back(i);
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t c) { return key_less(s[a], a, s[c], c); });
+  std::vector<float> w(n, 0.f);
+  for (size_t k = 0; k < kv; ++k) w[order[k]] = static_cast<float>(1.0 / static_cast<double>(kv));
+  if (scores_out) *scores_out = s;
+  return w;
+}
+
 // Centered clipping on the distance matrix alone (docs/GAR_SEMANTICS.md "Centered clipping"):
 // exactly `iters` rounds, every sum in index order.
 std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t nw, const std::vector<double>& a0,

@@ -40,6 +40,12 @@ std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t
 std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t nw, const std::vector<double>& a0,
                                  double tau, size_t f, size_t iters);
 
+// DnC spectral filtering (`iters` power rounds on K = -½ J D J, from D alone): weight 1 / kv on the
+// kv = min(m, |V|) valid rows of lowest (fp32 score, index), 0 elsewhere; scores[n] = λ u_i², +inf on
+// rows without a finite off-diagonal distance; none valid -> uniform 1/n and zero scores.
+std::vector<float> dnc_weights(const std::vector<double>& D, size_t n, size_t m, size_t iters,
+                               std::vector<float>* scores = nullptr);
+
 // Nearest-neighbour mixing on D alone (0 <= f < n, c = n - f; docs/GAR_SEMANTICS.md). nnm_mix: masks[2n]
 // (row i's set, i and its c - 1 nearest, as two 64-bit words; n <= 128) and the squared distances D' of
 // the mixed rows (+inf diagonal), for the selections above. nnm_unmix: the selection's weights a over

@@ -43,6 +43,13 @@ void geomed_select(const float* gram, int np, int n, int iters, double nu, float
 void cclip_select(const float* gram, int np, int n, int nw, const float* a0, double tau, int f, int iters,
                   float* weights, float* dists, hipStream_t stream, int batch = 1);
 
+// DnC spectral filtering (gar_dnc.hip): `iters` power rounds on K = -½ J D J of the Gram's distances
+// (n <= kMaxRows, K never stored); scores[n] = λ u_i², the squared projection of row i on the top
+// principal direction (+inf on rows without a finite distance); weights[n] = 1 / kv on the
+// kv = min(m, |V|) valid rows of lowest (score, index), 0 elsewhere. batch as krum_select.
+void dnc_select(const float* gram, int np, int n, int m, int iters, float* weights, float* scores,
+                hipStream_t stream, int batch = 1);
+
 // Nearest-neighbour mixing (gar_nnm.hip), n <= kMaxRows, 0 <= f < n, c = n - f. nnm_mix: from the Gram,
 // masks[n][2] (the set S_i of row i as two 64-bit words: i and its c - 1 nearest) and the pseudo-Gram
 // H [np][np] (H_ii = 0, H_ij = -D'_ij / 2 with D' the squared distances of the mixed rows), on which

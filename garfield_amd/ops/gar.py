@@ -391,6 +391,67 @@ def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> tor
     return _combine_rows(rows, _geomed_w(rows, iters, nu))
 
 
+# DnC spectral filtering (docs/GAR_SEMANTICS.md): the squared projection of every centred row on the top
+# principal direction equals λ u_i² for the top eigenpair of K = -½ J D J, so the scores come from a
+# fixed number of power rounds on the Gram's distances alone and end in a weight vector (1 / kv on the
+# kv lowest scores) for the combine kernels.
+
+
+def _dnc_args(n: int, f: int, m: int | None, iters) -> tuple:
+    """(m, iters): validates the spectral filter's own arguments."""
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError(f"dnc: expected an int iters >= 1, got {iters!r}")
+    if f < 0 or n < 2 * f + 1:
+        raise ValueError(f"dnc: expected 0 <= f and n >= 2f + 1, got n = {n}, f = {f}")
+    m = n - f if m is None else m
+    if not 1 <= m <= n:
+        raise ValueError(f"dnc: expected 1 <= m <= n, got m = {m}, n = {n}")
+    return int(m), iters
+
+
+def dnc_select(C, ws: Workspace, g: torch.Tensor, n: int, m: int, iters: int = 16) -> torch.Tensor:
+    """DnC weights [n] from a device Gram ``g`` (pitch gram_padded(n), n <= MAX_ROWS) by k_dnc_select; the
+    outlier scores land in the workspace's ``dnc_scores``. Every buffer comes from ``ws`` (capture-safe)."""
+    w = ws.get("weights", n)
+    C.gpu_dnc_select(g, n, m, iters, w, ws.get("dnc_scores", n))
+    return w
+
+
+def dnc_weights_from_distances(C, D: torch.Tensor, m: int, iters: int = 16) -> torch.Tensor:
+    """DnC weights [n] (fp32, CPU) from squared distances: the C++ path, else the oracle."""
+    if C is None:
+        return ref.dnc_weights(D, m, iters)[0]
+    return C.cpu_dnc_weights(D, m, iters)[0]
+
+
+def _dnc_w(rows: Rows, m: int, iters: int) -> torch.Tensor:
+    if rows.n > MAX_ROWS:   # the Gram's own device: large_gram on the GPU, no host round trip
+        return dnc_weights_from_gram(_large_gram(rows), m, iters)
+    C = _C_for(rows)
+    if rows.device.type == "cuda":
+        ws = workspace(rows)
+        return dnc_select(C, ws, _gram_into(C, rows, ws), rows.n, m, iters)
+    D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
+    return dnc_weights_from_distances(C, D, m, iters)
+
+
+def dnc_weights(gradients, f: int, m: int | None = None, iters: int = 16) -> torch.Tensor:
+    """Selection weights of DnC spectral filtering ([n] fp32 on the gradients' device): 1 / m on the
+    ``m`` (default ``n - f``) rows of lowest outlier score, the squared projection on the top principal
+    direction of the centred rows, from ``iters`` power rounds on the pairwise distances alone."""
+    rows = prepare(gradients)
+    m, iters = _dnc_args(rows.n, f, m, iters)
+    return _dnc_w(rows, m, iters)
+
+
+def dnc(gradients, f: int = 0, m: int | None = None, iters: int = 16, **_) -> torch.Tensor:
+    """DnC spectral filtering (Shejwalkar & Houmansadr, 2021; all coordinates, one filter): the average
+    of the rows kept by :func:`dnc_weights`."""
+    rows = prepare(gradients)
+    m, iters = _dnc_args(rows.n, f, m, iters)
+    return _combine_rows(rows, _dnc_w(rows, m, iters))
+
+
 # Centered clipping (CC; docs/GAR_SEMANTICS.md): v <- v + (1/n) Σ_i (x_i - v) min(1, tau / ||x_i - v||). The
 # centre stays an affine combination of the rows, so the rounds run on the Gram's distances alone and
 # end in a weight vector for the combine kernels. tau=None: the radius from the data, every round (the
@@ -1081,6 +1142,49 @@ def geomed_weights_from_gram(g: torch.Tensor, iters: int = 32, nu: float = 1e-6)
     return a.float()
 
 
+def dnc_weights_from_gram(g: torch.Tensor, m: int, iters: int = 16, with_scores: bool = False):
+    """DnC weights [n] (fp32, g's device; with the fp32 scores when ``with_scores``) from a Gram matrix
+    (vectorised in fp64, any n, no host round trip): reference.dnc_weights with the distances built as
+    the selection kernels build them, and rank masks in place of a host-side kv."""
+    n = g.shape[0]
+    dev = g.device
+    D = distances_from_gram(g).double()
+    D.fill_diagonal_(0.0)
+    fin = torch.isfinite(D)
+    fin.fill_diagonal_(False)
+    valid = fin.any(1)
+    D = torch.where(fin, D, torch.zeros_like(D))   # invalid rows and columns: all zero
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    nv = valid.sum()
+    nvd = nv.clamp(min=1).double()
+    ids = torch.arange(n, device=dev)
+    r = D.sum(1) / nvd
+    gm = r.sum() / nvd
+    kappa = torch.where(valid, r - 0.5 * gm, torch.full_like(r, -math.inf))
+    star = torch.where(kappa == kappa.max(), ids, torch.full_like(ids, n - 1)).min().reshape(1)
+    b = torch.where(valid, -0.5 * (D.index_select(1, star)[:, 0] - r - r.index_select(0, star) + gm), zero)
+    u = torch.zeros_like(b)
+    tiny = torch.finfo(torch.float64).tiny
+    for _ in range(iters):
+        nu = (b * b).sum().sqrt()
+        u = torch.where(nu > 0, b / nu.clamp(min=tiny), zero)
+        c = u.sum() / nvd
+        t = (D * torch.where(valid, u - c, zero)[None, :]).sum(1)
+        b = torch.where(valid, -0.5 * (t - t.sum() / nvd), zero)
+    lam = (u * b).sum()
+    s = torch.where(lam > 0, b * b / lam.clamp(min=tiny), zero).float()
+    s = torch.where(valid, s, torch.full_like(s, math.inf))
+    # rank by (fp32 score, index); invalid rows carry +inf and kv <= |V| keeps them out
+    before = (s[None, :] < s[:, None]) | ((s[None, :] == s[:, None]) & (ids[None, :] < ids[:, None]))
+    kv = nv.clamp(max=m)
+    keep = valid & (before.sum(1) < kv)
+    w = torch.where(keep, 1.0 / kv.clamp(min=1).double(), zero).float()
+    # no valid row (n == 1, every pair non-finite): uniform 1/n and zero scores, without a host branch
+    w = torch.where(nv > 0, w, torch.full_like(w, 1.0 / n))
+    s = torch.where(nv > 0, s, torch.zeros_like(s))
+    return (w, s) if with_scores else w
+
+
 def cclip_weights_from_gram(g: torch.Tensor, nw: int | None = None, a0: torch.Tensor | None = None,
                             tau: float | None = None, f: int = 0, iters: int = 3) -> torch.Tensor:
     """Centered-clipping weights [n] (fp32, g's device) from a Gram matrix (vectorised in fp64, any n, no
@@ -1201,6 +1305,7 @@ RULES = {
     "aksel": aksel,
     "geomed": geomed,
     "cclip": cclip,
+    "dnc": dnc,
     "nnm-cclip": lambda gradients, f=0, tau=None, iters=3, start="mean", m=None, **_: nnm(
         gradients, f, "cclip", tau=tau, iters=iters, start=start, m=m),
     "nnm-krum": lambda gradients, f, m=None, **_: nnm(gradients, f, "krum", m=m),

@@ -197,6 +197,99 @@ def cclip(G, f: int = 0, tau: float | None = None, iters: int = 3, start="mean",
     return combine(X, cclip_weights(D, n, a0, tau, f, iters))
 
 
+def dnc_scores(D: torch.Tensor, iters: int = 16) -> torch.Tensor:
+    """Outlier scores [n] (fp64, before the cast to fp32) of the DnC spectral filter on the squared distances
+    alone (docs/GAR_SEMANTICS.md "Spectral filtering"). With the rows centred at their mean, C Cᵀ = K = -½ J D J,
+    and the score of row i, its squared projection on the top right singular vector of C, is λ u_i² for the
+    top eigenpair (λ, u) of K. Exactly ``iters`` power rounds from the column of K at the row farthest from
+    the mean, sums in index order. +inf on rows without a finite off-diagonal distance; 0 if there is none."""
+    D = D.detach().to(device="cpu", dtype=torch.float64)
+    n = D.shape[0]
+    fin = [[i != j and math.isfinite(float(D[i, j])) for j in range(n)] for i in range(n)]
+    V = [i for i in range(n) if any(fin[i])]
+    if not V:
+        return torch.zeros(n, dtype=torch.float64)
+    nv = len(V)
+    dist = [[float(D[i, j]) if fin[i][j] else 0.0 for j in range(n)] for i in range(n)]
+    r = [0.0] * n
+    for i in V:
+        acc = 0.0
+        for j in V:
+            acc += dist[i][j]
+        r[i] = acc / nv
+    g = 0.0
+    for i in V:
+        g += r[i]
+    g /= nv
+    star = V[0]   # the lowest index in V that attains max κ, κ_i = r_i - g/2
+    for i in V:
+        if r[i] - 0.5 * g > r[star] - 0.5 * g:
+            star = i
+    b = [0.0] * n
+    for i in V:
+        b[i] = -0.5 * (dist[i][star] - r[i] - r[star] + g)
+    u = [0.0] * n
+    for _ in range(iters):
+        nu = 0.0
+        for i in V:
+            nu += b[i] * b[i]
+        nu = math.sqrt(nu)
+        c = 0.0
+        for i in V:
+            u[i] = b[i] / nu if nu > 0.0 else 0.0
+            c += u[i]
+        c /= nv
+        t = [0.0] * n
+        tm = 0.0
+        for i in V:
+            acc = 0.0
+            for j in V:
+                acc += dist[i][j] * (u[j] - c)
+            t[i] = acc
+            tm += acc
+        tm /= nv
+        for i in V:
+            b[i] = -0.5 * (t[i] - tm)
+    lam = 0.0
+    for i in V:
+        lam += u[i] * b[i]
+    s = torch.full((n,), math.inf, dtype=torch.float64)
+    for i in V:
+        s[i] = b[i] * b[i] / lam if lam > 0.0 else 0.0
+    return s
+
+
+def dnc_weights(D: torch.Tensor, m: int, iters: int = 16) -> tuple:
+    """(w [n], s [n]), both fp32: the scores of :func:`dnc_scores` cast to fp32, and weight 1 / kv on the
+    kv = min(m, |V|) valid rows lowest by (fp32 score, index), 0 elsewhere; no valid row: uniform 1/n."""
+    n = D.shape[0]
+    s = dnc_scores(D, iters).float()
+    Df = D.detach().to(device="cpu", dtype=torch.float64)
+    V = [i for i in range(n) if any(j != i and math.isfinite(float(Df[i, j])) for j in range(n))]
+    if not V:
+        return torch.full((n,), 1.0 / n, dtype=torch.float64).float(), s
+    kv = min(m, len(V))
+    w = torch.zeros(n, dtype=torch.float64)
+    for i in _order(s.tolist(), V)[:kv]:
+        w[i] = 1.0 / kv
+    return w.float(), s
+
+
+def dnc_svd_scores(G) -> torch.Tensor:
+    """The paper's outlier scores [n] (fp64) on the vectors themselves: the squared projection of every
+    centred row on the top right singular vector of the centred matrix (all coordinates, finite rows)."""
+    X = _g(G)
+    C = X - X.mean(dim=0, keepdim=True)
+    v = torch.linalg.svd(C, full_matrices=False).Vh[0]
+    return (C @ v) ** 2
+
+
+def dnc(G, f: int, m: int | None = None, iters: int = 16) -> torch.Tensor:
+    X = _g(G)
+    m = X.shape[0] - f if m is None else m
+    return combine(X, dnc_weights(pairwise_sqdist(X), m, iters)[0].double())
+
+
 # Nearest-neighbour mixing (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing"): every gradient is
 # replaced by the mean of its c = n - f nearest gradients, itself included, before a rule runs.
 # Mixing is linear, so everything below works on the squared distances alone.

@@ -49,13 +49,13 @@ from garfield_amd.utils.profiling import PhaseTimer
 # the first convolution; users may override the variable explicitly.
 os.environ.setdefault("MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_WRW_XDLOPS", "0")
 
-WEIGHTED_RULES = {"average", "krum", "brute", "aksel", "geomed", "cclip"}
+WEIGHTED_RULES = {"average", "krum", "brute", "aksel", "geomed", "cclip", "dnc"}
 _LP_MODULES = (nn.modules.conv._ConvNd, nn.Linear)
 COORD_RULES = {"median", "trimmed-mean", "averaged-median", "average-nan", "condense", "bulyan"}
 # coordinate-wise rules accepted behind pre_aggregation="nnm" (gar.nnm_coord; "nnm-median" exists through
 # the functional interface and the registry only)
 NNM_ENGINE_COORD_RULES = ("trimmed-mean",)
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip"}   # per-layer != flat only for distance-based rules
+LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip", "dnc"}   # per-layer != flat only for distance-based rules
 # Layer-wise Krum as device operations (gar_layerwise.hip: one segmented Gram launch, a batched
 # selection, one segmented combine + SGD); "0" runs the per-segment loop (the reference form).
 LW_DEVICE = os.environ.get("GARFIELD_LW_DEVICE", "1") != "0"
@@ -562,14 +562,14 @@ class RobustDataParallel:
             gkw = dict(kw)
             if rule not in ("average", "median", "average-nan"):
                 gkw["f"] = cfg.f
-            if cfg.m is not None and rule in ("krum", "bulyan"):
+            if cfg.m is not None and rule in ("krum", "bulyan", "dnc"):
                 gkw["m"] = cfg.m
             if rule == "condense":
                 gkw.setdefault("seed", cfg.seed + self.step_count)
             if cfg.pre_aggregation and rule in NNM_ENGINE_COORD_RULES:   # no weights: the rule over the set means
                 self.last_weights = None
                 g = gar.nnm_coord(self.G.float(), cfg.f, rule).float()
-            elif rule in ("geomed", "cclip") or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
+            elif rule in ("geomed", "cclip", "dnc") or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
                 self.last_weights = w = self._weights(rule, kw, self.G.float())
                 g = gar.combine(self.G.float(), w).float()
             else:
@@ -604,10 +604,10 @@ class RobustDataParallel:
         the segment with the rule itself."""
         cfg = self.cfg
         gkw = dict(kw, f=cfg.f)
-        if cfg.m is not None and rule in ("krum", "bulyan"):
+        if cfg.m is not None and rule in ("krum", "bulyan", "dnc"):
             gkw["m"] = cfg.m
         cuda = self.device.type == "cuda"
-        if cuda and LW_DEVICE and self.n <= gar.MAX_ROWS and (rule in ("krum", "geomed", "cclip")
+        if cuda and LW_DEVICE and self.n <= gar.MAX_ROWS and (rule in ("krum", "geomed", "cclip", "dnc")
                                                               or (rule == "bulyan" and self.n <= 64)):
             self._layerwise_device(rule, first)
             return
@@ -690,6 +690,9 @@ class RobustDataParallel:
                 C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
             C.gpu_cclip_select(lw["gram"], n, n, lw["w"] if start == "krum" else None, tau, f, iters, lw["w"],
                                lw["dists"], lw["L"])
+        elif rule == "dnc":   # every segment's power rounds and selection in one batched launch
+            C.gpu_dnc_select(lw["gram"], n, cfg.m if cfg.m is not None else n - f, self._dnc_iters(cfg.gar_kwargs),
+                             lw["w"], lw["scores"], lw["L"])
         else:
             C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
         C.gpu_lw_combine_sgd(G, lw["jobs"], lw["seg_off"], 0, lw["w"], self.flat.data[: self.d], self.mom[: self.d],
@@ -715,12 +718,19 @@ class RobustDataParallel:
             return gar.geomed_weights(G, *self._geomed_args(kw))
         if rule == "cclip":
             return gar.cclip_weights(G, f, **self._cclip_kwargs(kw))
+        if rule == "dnc":
+            return gar.dnc_weights(G, f, self.cfg.m, self._dnc_iters(kw))
         return gar.aksel_weights(G, f, kw.get("mode", "mid"))
 
     @staticmethod
     def _geomed_args(kw: dict) -> tuple:
         """(iters, nu) of the geometric median from the rule's keyword arguments."""
         return int(kw.get("iters", 32)), float(kw.get("nu", 1e-6))
+
+    @staticmethod
+    def _dnc_iters(kw: dict) -> int:
+        """The power-iteration count of DnC from the rule's keyword arguments (validated at construction)."""
+        return kw.get("iters", 16)
 
     @staticmethod
     def _cclip_args(kw: dict) -> tuple:
@@ -773,7 +783,7 @@ class RobustDataParallel:
         kw = dict(cfg.gar_kwargs)
         if cfg.gar not in ("average", "median", "average-nan"):
             kw["f"] = cfg.f
-        if cfg.m is not None and cfg.gar in ("krum", "bulyan"):
+        if cfg.m is not None and cfg.gar in ("krum", "bulyan", "dnc"):
             kw["m"] = cfg.m
         if cfg.gar == "condense":
             kw.setdefault("seed", cfg.seed + self.step_count)
@@ -800,6 +810,8 @@ class RobustDataParallel:
                     w = gar.geomed_weights(rows, *self._geomed_args(cfg.gar_kwargs))
                 elif cfg.gar == "cclip":
                     w = gar.cclip_weights(rows, cfg.f, **self._cclip_kwargs(cfg.gar_kwargs))
+                elif cfg.gar == "dnc":
+                    w = gar.dnc_weights(rows, cfg.f, cfg.m, self._dnc_iters(cfg.gar_kwargs))
                 else:
                     w = torch.full((len(rows),), 1.0 / len(rows), device=self.device)
                 self.last_weights = w
@@ -819,7 +831,7 @@ class RobustDataParallel:
             # as a [rows, d] fp32 matrix: the aggregate keeps fp32 (a list of 16-bit rows
             # would round it to the rows' dtype), as the synchronous step's
             X = torch.stack([r.float() for r in rows])
-            if (cfg.pre_aggregation or cfg.gar == "cclip") and cfg.gar not in NNM_ENGINE_COORD_RULES:
+            if (cfg.pre_aggregation or cfg.gar in ("cclip", "dnc")) and cfg.gar not in NNM_ENGINE_COORD_RULES:
                 self.last_weights = w = self._weights(cfg.gar, dict(cfg.gar_kwargs), X)
                 g = gar.combine(X, w).float()
             else:

@@ -61,8 +61,8 @@ from garfield_amd.parallel.comm import collectives_on, gloo_backend, world1_coll
 from garfield_amd.parallel.rccl import direct_backend
 from garfield_amd.parallel.signals import Handoff
 
-DISTANCE_RULES = {"krum", "brute", "bulyan", "geomed", "cclip"}
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip"}
+DISTANCE_RULES = {"krum", "brute", "bulyan", "geomed", "cclip", "dnc"}
+LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip", "dnc"}
 SUPPORTED = DISTANCE_RULES | {"average", "aksel", "median", "trimmed-mean", "averaged-median", "average-nan",
                               "condense"}
 
@@ -78,7 +78,7 @@ def layerwise_device_ok(rule: str, n: int, f: int) -> bool:
         return n - 2 * f - 2 <= 64
     if rule == "brute":
         return n <= 64
-    return True   # krum, geomed, cclip (batched one-workgroup selections: n <= MAX_ROWS), aksel
+    return True   # krum, geomed, cclip, dnc (batched one-workgroup selections: n <= MAX_ROWS), aksel
 
 
 def shard_pad(world: int, base: int = 64) -> int:
@@ -634,7 +634,7 @@ class ShardedAggregator:
             mats[b.lo] = self._matrix(b)
         if rule == "brute":   # C(n, f) subsets of n > 128 rows: the device search takes n <= 64
             raise ValueError(f"brute: n must be <= 64 on the GPU (n = {n})")
-        if rule in ("krum", "bulyan", "geomed", "cclip"):
+        if rule in ("krum", "bulyan", "geomed", "cclip", "dnc"):
             total = None
             for b in self.buckets:
                 g = gar.large_gram(mats[b.lo])                  # MFMA, fp32 (gar_large.hip)
@@ -649,6 +649,8 @@ class ShardedAggregator:
                 ck = e._cclip_kwargs(kw)
                 a0 = gar.large_select(gs, f, m) if ck["start"] == "krum" else None
                 ws = gar.cclip_weights_from_gram(gs, n, a0, ck["tau"], f, ck["iters"])
+            elif rule == "dnc":   # after the partial Grams are summed: the same selection on every rank
+                ws = gar.dnc_weights_from_gram(gs, cfg.m if cfg.m is not None else n - f, e._dnc_iters(kw))
             else:
                 W = gar.large_select(gs, f, m, bulyan=True)
                 Wm = torch.empty_like(W)
@@ -717,6 +719,9 @@ class ShardedAggregator:
             return w
         if rule == "cclip":
             return gar.cclip_select(C, ws, gram_total, n, n, f, *self.e._cclip_args(cfg.gar_kwargs), m)
+        if rule == "dnc":
+            return gar.dnc_select(C, ws, gram_total, n, cfg.m if cfg.m is not None else n - f,
+                                  self.e._dnc_iters(cfg.gar_kwargs))
         if rule == "brute":
             if n > 64:
                 raise ValueError("brute: n must be <= 64 on the GPU")
@@ -867,6 +872,9 @@ class ShardedAggregator:
                         C.gpu_krum_select(total, n, f, m, plan["w"], plan["order"], plan["scores"], L)
                     C.gpu_cclip_select(total, n, n, plan["w"] if start == "krum" else None, tau, f, iters, plan["w"],
                                        plan["dists"], L)
+                elif rule == "dnc":
+                    C.gpu_dnc_select(total, n, cfg.m if cfg.m is not None else n - f, e._dnc_iters(cfg.gar_kwargs),
+                                     plan["w"], plan["scores"], L)
                 else:
                     C.gpu_krum_select(total, n, f, m, plan["w"], plan["order"], plan["scores"], L)
             e.last_weights = plan["w"]
@@ -905,6 +913,9 @@ class ShardedAggregator:
                     W[si] = (Cn.cpu_geomed_weights(Ds, *ga) if Cn is not None else ref.geomed_weights(Ds, *ga)).float()
                 elif rule == "cclip":
                     W[si] = gar.cclip_weights_from_distances(Cn, Ds, n, f, *e._cclip_args(cfg.gar_kwargs), m)
+                elif rule == "dnc":
+                    W[si] = gar.dnc_weights_from_distances(Cn, Ds, cfg.m if cfg.m is not None else n - f,
+                                                           e._dnc_iters(cfg.gar_kwargs))
                 elif rule == "brute":
                     W[si] = (Cn.cpu_brute_weights(Ds, f) if Cn is not None else ref.brute_weights(Ds, f)).float()
                 else:
@@ -981,6 +992,8 @@ class ShardedAggregator:
                 w = C.cpu_geomed_weights(D, *ga) if C is not None else ref.geomed_weights(D, *ga).float()
             elif rule == "cclip":
                 w = gar.cclip_weights_from_distances(C, D, n, f, *e._cclip_args(kw), m)
+            elif rule == "dnc":
+                w = gar.dnc_weights_from_distances(C, D, cfg.m if cfg.m is not None else n - f, e._dnc_iters(kw))
             else:
                 w = C.cpu_brute_weights(D, f) if C is not None else ref.brute_weights(D, f).float()
             e.last_weights = w

@@ -25,14 +25,14 @@ __device__ __forceinline__ void gather_weighted(const RowTable& rows, const int*
     load_vec<DT, 8>(rows.p[sel[j + 3]], x, v3);
     const float w0 = wsel[j], w1 = wsel[j + 1], w2 = wsel[j + 2], w3 = wsel[j + 3];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] += w0 * v0[c] + w1 * v1[c] + w2 * v2[c] + w3 * v3[c];
+    for (int c = 0; c < 8; ++c) acc[c] = weighted_acc4(acc[c], w0, v0[c], w1, v1[c], w2, v2[c], w3, v3[c]);
   }
   for (; j < cnt; ++j) {
     float v[8];
     load_vec<DT, 8>(rows.p[sel[j]], x, v);
     const float w = wsel[j];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] += w * v[c];
+    for (int c = 0; c < 8; ++c) acc[c] = weighted_acc1(acc[c], w, v[c]);
   }
 }
 
@@ -40,7 +40,7 @@ template <int DT>
 __device__ __forceinline__ float gather_weighted_one(const RowTable& rows, const int* sel, const float* wsel,
                                                      int cnt, int64_t x) {
   float a = 0.f;
-  for (int j = 0; j < cnt; ++j) a += wsel[j] * load_one<DT>(rows.p[sel[j]], x);
+  for (int j = 0; j < cnt; ++j) a = weighted_acc1(a, wsel[j], load_one<DT>(rows.p[sel[j]], x));
   return a;
 }
 
@@ -149,16 +149,6 @@ template <int DT> struct Collude {
   }
 };
 
-__device__ __forceinline__ float sgd_apply(float g, float& p, float& buf, const SgdArgs& a) {
-  if (a.weight_decay != 0.f) g += a.weight_decay * p;
-  if (a.momentum != 0.f) {
-    buf = a.first_step ? g : a.momentum * buf + (1.f - a.dampening) * g;
-    g = a.nesterov ? g + a.momentum * buf : buf;
-  }
-  p -= a.lr * g;
-  return g;
-}
-
 template <int DT>
 __global__ __launch_bounds__(256) void k_combine_sgd(RowTable rows, int n, int64_t d,
                                                      const float* __restrict__ weights, float* __restrict__ param,
@@ -181,7 +171,7 @@ __global__ __launch_bounds__(256) void k_combine_sgd(RowTable rows, int n, int64
       bv[0] = b0.x; bv[1] = b0.y; bv[2] = b0.z; bv[3] = b0.w; bv[4] = b1.x; bv[5] = b1.y; bv[6] = b1.z; bv[7] = b1.w;
     }
 #pragma unroll
-    for (int c = 0; c < 8; ++c) sgd_apply(acc[c], pv[c], bv[c], args);
+    for (int c = 0; c < 8; ++c) sgd_update(acc[c], pv[c], bv[c], args);
     *reinterpret_cast<float4*>(param + x) = make_float4(pv[0], pv[1], pv[2], pv[3]);
     *reinterpret_cast<float4*>(param + x + 4) = make_float4(pv[4], pv[5], pv[6], pv[7]);
     if (shadow) store_vec<8>(shadow, shadow_dt, x, pv);
@@ -196,7 +186,7 @@ __global__ __launch_bounds__(256) void k_combine_sgd(RowTable rows, int n, int64
       if (grad_out) grad_out[x] = g;
       float p = param[x];
       float b = (args.momentum != 0.f && !args.first_step) ? mom[x] : 0.f;
-      sgd_apply(g, p, b, args);
+      sgd_update(g, p, b, args);
       param[x] = p;
       if (shadow) store_one(shadow, shadow_dt, x, p);
       if (args.momentum != 0.f) mom[x] = b;

@@ -85,6 +85,40 @@ template <int DT> __device__ __forceinline__ float load_one(const void* base, in
   else return cvt16<DT>(static_cast<const uint16_t*>(base)[x]);
 }
 
+// The weighted-combine arithmetic in a FIXED rounding order, shared by every kernel whose results
+// must agree bit for bit (k_combine, k_combine_sgd, k_lw_combine_sgd's 8-wide groups and the single
+// elements of a group that a job edge splits). Written as `acc += w0 * v0 + w1 * v1 + w2 * v2 + w3 * v3`
+// the compiler chooses which product stays a rounded multiply and which become fused multiply-adds, and
+// it chooses differently from one kernel, and from one lane of a packed instruction, to the next.
+// acc4: acc + fma(w3, v3, fma(w2, v2, fma(w0, v0, w1 * v1))), the order the fp32 k_combine_sgd had;
+// acc1: fma(w, v, acc).
+__device__ __forceinline__ float weighted_acc4(float acc, float w0, float v0, float w1, float v1, float w2, float v2,
+                                               float w3, float v3) {
+#pragma clang fp contract(off)
+  const float p = w1 * v1;
+  return acc + __builtin_fmaf(w3, v3, __builtin_fmaf(w2, v2, __builtin_fmaf(w0, v0, p)));
+}
+__device__ __forceinline__ float weighted_acc1(float acc, float w, float v) { return __builtin_fmaf(w, v, acc); }
+
+// The fused SGD update of one element, in a fixed rounding order for the same reason (left to the
+// compiler, k_combine_sgd's 8-wide path summed two rounded products for the momentum buffer where its
+// scalar tail and k_lw_combine_sgd fused one of them): every step is one fused multiply-add, the
+// buffer fma(1 - dampening, g, momentum * buf). With dampening = 0 both forms give the same bits.
+__device__ __forceinline__ void sgd_update(float g, float& p, float& buf, const SgdArgs& a) {
+#pragma clang fp contract(off)
+  if (a.weight_decay != 0.f) g = __builtin_fmaf(a.weight_decay, p, g);
+  if (a.momentum != 0.f) {
+    if (!a.first_step) {
+      const float mb = a.momentum * buf;
+      buf = __builtin_fmaf(1.f - a.dampening, g, mb);
+    } else {
+      buf = g;
+    }
+    g = a.nesterov ? __builtin_fmaf(a.momentum, buf, g) : buf;
+  }
+  p = __builtin_fmaf(-a.lr, g, p);
+}
+
 __device__ __forceinline__ void store_one(void* out, int out_dt, int64_t x, float v) {
   if (out_dt == kF32) static_cast<float*>(out)[x] = v;
   else if (out_dt == kBF16) static_cast<uint16_t*>(out)[x] = f_to_bf16(v);

@@ -197,19 +197,20 @@ __device__ __forceinline__ void gather8(const RowTable& rows, const int* sel, co
     load8_any<DT>(rows.p[sel[j + 3]], x, v3);
     const float w0 = wsel[j], w1 = wsel[j + 1], w2 = wsel[j + 2], w3 = wsel[j + 3];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] += w0 * v0[c] + w1 * v1[c] + w2 * v2[c] + w3 * v3[c];
+    for (int c = 0; c < 8; ++c) acc[c] = weighted_acc4(acc[c], w0, v0[c], w1, v1[c], w2, v2[c], w3, v3[c]);
   }
   for (; j < cnt; ++j) {
     float v[8];
     load8_any<DT>(rows.p[sel[j]], x, v);
     const float w = wsel[j];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) acc[c] += w * v[c];
+    for (int c = 0; c < 8; ++c) acc[c] = weighted_acc1(acc[c], w, v[c]);
   }
 }
 
-// one element with gather8's arithmetic (4 rows per step): a group's elements that a job boundary
-// splits (a shard edge inside an 8-wide group) get the bits the 8-wide path would give them
+// one element with gather8's arithmetic (4 rows per step, weighted_acc4's fixed rounding order): a
+// group's elements that a job boundary splits (a shard edge inside an 8-wide group) get the bits the
+// 8-wide path would give them
 template <int DT>
 __device__ __forceinline__ float gather1_grouped(const RowTable& rows, const int* sel, const float* wsel, int cnt,
                                                  int64_t x) {
@@ -219,19 +220,10 @@ __device__ __forceinline__ float gather1_grouped(const RowTable& rows, const int
     const float v0 = load_one<DT>(rows.p[sel[j]], x), v1 = load_one<DT>(rows.p[sel[j + 1]], x);
     const float v2 = load_one<DT>(rows.p[sel[j + 2]], x), v3 = load_one<DT>(rows.p[sel[j + 3]], x);
     const float w0 = wsel[j], w1 = wsel[j + 1], w2 = wsel[j + 2], w3 = wsel[j + 3];
-    acc += w0 * v0 + w1 * v1 + w2 * v2 + w3 * v3;
+    acc = weighted_acc4(acc, w0, v0, w1, v1, w2, v2, w3, v3);
   }
-  for (; j < cnt; ++j) acc += wsel[j] * load_one<DT>(rows.p[sel[j]], x);
+  for (; j < cnt; ++j) acc = weighted_acc1(acc, wsel[j], load_one<DT>(rows.p[sel[j]], x));
   return acc;
-}
-
-__device__ __forceinline__ void sgd_one(float g, float& p, float& buf, const SgdArgs& a) {
-  if (a.weight_decay != 0.f) g += a.weight_decay * p;
-  if (a.momentum != 0.f) {
-    buf = a.first_step ? g : a.momentum * buf + (1.f - a.dampening) * g;
-    g = a.nesterov ? g + a.momentum * buf : buf;
-  }
-  p -= a.lr * g;
 }
 
 // jobs: (start, end, segment) in LOCAL coordinates of the rows / param / mom / shadow; base: the
@@ -261,7 +253,7 @@ __global__ __launch_bounds__(256) void k_lw_combine_sgd(RowTable rows, int n, co
   auto update = [&](int64_t x, float g) {
     float p = param[x];
     float bf = (args.momentum != 0.f && !args.first_step) ? mom[x] : 0.f;
-    sgd_one(g, p, bf, args);
+    sgd_update(g, p, bf, args);
     param[x] = p;
     if (shadow) store_one(shadow, shadow_dt, x, p);
     if (args.momentum != 0.f) mom[x] = bf;
@@ -274,7 +266,7 @@ __global__ __launch_bounds__(256) void k_lw_combine_sgd(RowTable rows, int n, co
   const int64_t ve = va + ((ve_max > va ? ve_max - va : 0) & ~static_cast<int64_t>(7));   // end of whole groups
   auto tail_one = [&](int64_t x) {
     float g = 0.f;
-    for (int j = 0; j < cnt; ++j) g += wsel[j] * load_one<DT>(rows.p[sel[j]], x);
+    for (int j = 0; j < cnt; ++j) g = weighted_acc1(g, wsel[j], load_one<DT>(rows.p[sel[j]], x));
     return g;
   };
   for (int64_t x = a + threadIdx.x; x < (va < b ? va : b); x += 256)        // a split group's head

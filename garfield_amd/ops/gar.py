@@ -28,19 +28,28 @@ the GPU, up to ``LARGE_ROWS`` (1024) rows run on ``gar_large.hip`` as one [n, d]
 tail by LDS radix select; the Krum/Bulyan Gram as a split-K MFMA kernel with fp32 output and
 Bulyan's W·X on fp32 MFMA);
 everything else, and the CPU, uses a vectorised PyTorch implementation.
+
+The distance-based selections (Krum, geometric median, centered clipping, DnC, Brute, Bulyan, and the
+mixing in front of them) are resolved and dispatched in ``ops/selection.py``; :func:`selection_weights`
+picks the backend for a gradient set.
 """
 from __future__ import annotations
 
 import math
 import threading
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import torch
 
 from garfield_amd import _native
 from garfield_amd.ops import reference as ref
+# the distance-based selections live in ops/selection.py; their Gram forms keep their names here
+from garfield_amd.ops.selection import (BRUTE_MAX_SUBSETS, CCLIP_STARTS, MAX_ROWS, NNM_RULES,  # noqa: F401
+                                        Selection, cclip_weights_from_gram, distances_from_gram,
+                                        dnc_weights_from_gram, geomed_weights_from_gram, krum_weights_from_gram,
+                                        large_bulyan_weights as _large_bulyan_weights, large_select,
+                                        nan_inf as _nan_inf, nnm_from_gram, resolve)
 
-MAX_ROWS = 128
 LARGE_ROWS = 1024
 _LARGE_MODE = {"median": 0, "trimmed-mean": 1, "averaged-median": 2}
 
@@ -76,7 +85,9 @@ def _aligned(t: torch.Tensor) -> bool:
 
 
 def prepare(gradients) -> Rows:
-    """Validate and normalise a gradient set (list of tensors or [n, d] tensor)."""
+    """Validate and normalise a gradient set (list of tensors or [n, d] tensor; prepared rows pass through)."""
+    if isinstance(gradients, Rows):
+        return gradients
     if isinstance(gradients, torch.Tensor):
         if gradients.dim() == 1:
             gradients = gradients.unsqueeze(0)
@@ -309,39 +320,36 @@ def average(gradients, **_) -> torch.Tensor:
     return _finish(rows.stacked().float().mean(0) if rows.dtype != torch.float64 else rows.stacked().mean(0), rows)
 
 
+def selection_weights(gradients, sel: Selection) -> torch.Tensor:
+    """The weights of the resolved selection ``sel`` over a gradient set ([n] fp32 on the gradients' device;
+    Bulyan: W [t, n]). The one place the backend is picked, by (n, device, extension): the device kernels on
+    the workspace's Gram; beyond their rows the form vectorised on the Gram where the rule has one; else
+    fp64 squared distances into the C++ functions or the oracle."""
+    rows = prepare(gradients)
+    C = _C_for(rows)
+    cuda = rows.device.type == "cuda"
+    if cuda and rows.n <= sel.device_rows:
+        ws = workspace(rows)
+        return sel.on_device(C, _gram_into(C, rows, ws), ws)
+    if rows.n > MAX_ROWS and sel.has_gram_form(cuda):   # the Gram's own device: large_gram on the GPU, no host round trip
+        return sel.from_gram(_large_gram(rows))
+    if cuda:
+        D = pairwise_distances(rows.obj)
+    else:
+        D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
+    return sel.on_host(C, D).to(rows.device)
+
+
 def krum_weights(gradients, f: int, m: int | None = None, pre: str | None = None) -> torch.Tensor:
     """Selection weights of Multi-Krum ([n] fp32 on the gradients' device); ``pre="nnm"``: the row
     weights of Krum applied after nearest-neighbour mixing (:func:`nnm_weights`)."""
     rows = prepare(gradients)
-    if pre is not None:
-        return _nnm_w(rows, f, "krum", _pre=pre, m=m)
-    m = rows.n - f - 2 if m is None else m
-    return _krum_weights(rows, f, m)
-
-
-def _krum_weights(rows: Rows, f: int, m: int) -> torch.Tensor:
-    if rows.n > MAX_ROWS:
-        return _large_krum_weights(rows, f, m)
-    C = _C_for(rows)
-    if rows.device.type == "cuda":
-        ws = workspace(rows)
-        g = _gram_into(C, rows, ws)
-        w = ws.get("weights", rows.n)
-        order = ws.get("order", rows.n, torch.int32)
-        scores = ws.get("scores", rows.n)
-        C.gpu_krum_select(g, rows.n, f, m, w, order, scores)
-        return w
-    if C is None:
-        return ref.krum_weights(ref.pairwise_sqdist(rows.stacked()), f, m).float()
-    w, _ = C.cpu_krum_weights(C.cpu_pairwise(rows.obj), f, m)
-    return w
+    return selection_weights(rows, resolve("krum", rows.n, f, m, pre))
 
 
 def krum(gradients, f: int, m: int | None = None, **_) -> torch.Tensor:
     rows = prepare(gradients)
-    m = rows.n - f - 2 if m is None else m
-    w = _krum_weights(rows, f, m)
-    return _combine_rows(rows, w)
+    return _combine_rows(rows, krum_weights(rows, f, m))
 
 
 def _combine_rows(rows: Rows, w: torch.Tensor) -> torch.Tensor:
@@ -363,32 +371,15 @@ def geomed_weights(gradients, iters: int = 32, nu: float = 1e-6, pre: str | None
     """Weights of the geometric median ([n] fp32 on the gradients' device): ``iters`` rounds of
     smoothed Weiszfeld (RFA) iterated on the pairwise distances alone. ``pre="nnm"``: the row weights
     of the geometric median of the rows mixed over their ``n - f`` nearest (:func:`nnm_weights`)."""
-    if pre is not None:
-        return _nnm_w(prepare(gradients), f, "geomed", _pre=pre, iters=iters, nu=nu)
-    return _geomed_w(prepare(gradients), iters, nu)
-
-
-def _geomed_w(rows: Rows, iters: int, nu: float) -> torch.Tensor:
-    if rows.n > MAX_ROWS:   # the Gram's own device: large_gram on the GPU, no host round trip
-        return geomed_weights_from_gram(_large_gram(rows), iters, nu)
-    C = _C_for(rows)
-    if rows.device.type == "cuda":
-        ws = workspace(rows)
-        g = _gram_into(C, rows, ws)
-        w = ws.get("weights", rows.n)
-        dists = ws.get("geomed_dists", rows.n)
-        C.gpu_geomed_select(g, rows.n, iters, nu, w, dists)
-        return w
-    if C is None:
-        return ref.geomed_weights(ref.pairwise_sqdist(rows.stacked()), iters, nu).float()
-    return C.cpu_geomed_weights(C.cpu_pairwise(rows.obj), iters, nu)
+    rows = prepare(gradients)
+    return selection_weights(rows, resolve("geomed", rows.n, f, None, pre, {"iters": iters, "nu": nu}))
 
 
 def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> torch.Tensor:
     """Geometric median (minimiser of the sum of L2 distances; breakdown point 1/2, so ``f`` only
     enters the registry's check): Σ_i a_i g_i with the weights of :func:`geomed_weights`."""
     rows = prepare(gradients)
-    return _combine_rows(rows, _geomed_w(rows, iters, nu))
+    return _combine_rows(rows, geomed_weights(rows, iters, nu))
 
 
 # DnC spectral filtering (docs/GAR_SEMANTICS.md): the squared projection of every centred row on the top
@@ -397,132 +388,25 @@ def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> tor
 # kv lowest scores) for the combine kernels.
 
 
-def _dnc_args(n: int, f: int, m: int | None, iters) -> tuple:
-    """(m, iters): validates the spectral filter's own arguments."""
-    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
-        raise ValueError(f"dnc: expected an int iters >= 1, got {iters!r}")
-    if f < 0 or n < 2 * f + 1:
-        raise ValueError(f"dnc: expected 0 <= f and n >= 2f + 1, got n = {n}, f = {f}")
-    m = n - f if m is None else m
-    if not 1 <= m <= n:
-        raise ValueError(f"dnc: expected 1 <= m <= n, got m = {m}, n = {n}")
-    return int(m), iters
-
-
-def dnc_select(C, ws: Workspace, g: torch.Tensor, n: int, m: int, iters: int = 16) -> torch.Tensor:
-    """DnC weights [n] from a device Gram ``g`` (pitch gram_padded(n), n <= MAX_ROWS) by k_dnc_select; the
-    outlier scores land in the workspace's ``dnc_scores``. Every buffer comes from ``ws`` (capture-safe)."""
-    w = ws.get("weights", n)
-    C.gpu_dnc_select(g, n, m, iters, w, ws.get("dnc_scores", n))
-    return w
-
-
-def dnc_weights_from_distances(C, D: torch.Tensor, m: int, iters: int = 16) -> torch.Tensor:
-    """DnC weights [n] (fp32, CPU) from squared distances: the C++ path, else the oracle."""
-    if C is None:
-        return ref.dnc_weights(D, m, iters)[0]
-    return C.cpu_dnc_weights(D, m, iters)[0]
-
-
-def _dnc_w(rows: Rows, m: int, iters: int) -> torch.Tensor:
-    if rows.n > MAX_ROWS:   # the Gram's own device: large_gram on the GPU, no host round trip
-        return dnc_weights_from_gram(_large_gram(rows), m, iters)
-    C = _C_for(rows)
-    if rows.device.type == "cuda":
-        ws = workspace(rows)
-        return dnc_select(C, ws, _gram_into(C, rows, ws), rows.n, m, iters)
-    D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
-    return dnc_weights_from_distances(C, D, m, iters)
-
-
 def dnc_weights(gradients, f: int, m: int | None = None, iters: int = 16) -> torch.Tensor:
     """Selection weights of DnC spectral filtering ([n] fp32 on the gradients' device): 1 / m on the
     ``m`` (default ``n - f``) rows of lowest outlier score, the squared projection on the top principal
     direction of the centred rows, from ``iters`` power rounds on the pairwise distances alone."""
     rows = prepare(gradients)
-    m, iters = _dnc_args(rows.n, f, m, iters)
-    return _dnc_w(rows, m, iters)
+    return selection_weights(rows, resolve("dnc", rows.n, f, m, None, {"iters": iters}))
 
 
 def dnc(gradients, f: int = 0, m: int | None = None, iters: int = 16, **_) -> torch.Tensor:
     """DnC spectral filtering (Shejwalkar & Houmansadr, 2021; all coordinates, one filter): the average
     of the rows kept by :func:`dnc_weights`."""
     rows = prepare(gradients)
-    m, iters = _dnc_args(rows.n, f, m, iters)
-    return _combine_rows(rows, _dnc_w(rows, m, iters))
+    return _combine_rows(rows, dnc_weights(rows, f, m, iters))
 
 
 # Centered clipping (CC; docs/GAR_SEMANTICS.md): v <- v + (1/n) Σ_i (x_i - v) min(1, tau / ||x_i - v||). The
 # centre stays an affine combination of the rows, so the rounds run on the Gram's distances alone and
 # end in a weight vector for the combine kernels. tau=None: the radius from the data, every round (the
 # (|V| - f)-th smallest distance of the centre to a worker).
-
-CCLIP_STARTS = ("mean", "krum")
-
-
-def _cclip_args(n: int, f: int, tau, iters, start, m: int | None = None) -> tuple:
-    """(tau as the launchers take it, iters, m): validates centered clipping's own arguments."""
-    if iters is None or int(iters) < 1:
-        raise ValueError(f"cclip: expected iters >= 1, got {iters}")
-    if tau is not None and not float(tau) > 0.0:
-        raise ValueError(f"cclip: expected tau None (from the data) or > 0, got {tau}")
-    if f < 0:
-        raise ValueError(f"cclip: expected f >= 0, got {f}")
-    if isinstance(start, str):
-        if start not in CCLIP_STARTS:
-            raise ValueError(f"cclip: unknown start {start!r}; available: {CCLIP_STARTS} or an [n] weight tensor")
-        if start == "krum":
-            m = n - f - 2 if m is None else m
-            if n < 2 * f + 3 or not 1 <= m <= n - f - 2:   # Krum's own requirement, as on every other path
-                raise ValueError(f"cclip: start='krum' expects n >= 2f + 3 and 1 <= m <= n - f - 2, got n = {n}, "
-                                 f"f = {f}, m = {m}")
-    elif not isinstance(start, torch.Tensor) or start.numel() != n:
-        raise ValueError(f"cclip: start must be one of {CCLIP_STARTS} or an [n] weight tensor (n = {n})")
-    return (0.0 if tau is None else float(tau)), int(iters), m
-
-
-def cclip_select(C, ws: Workspace, g: torch.Tensor, n: int, nw: int, f: int, tau: float, iters: int, start="mean",
-                 m: int | None = None) -> torch.Tensor:
-    """Centered-clipping weights [n] from a device Gram ``g`` (pitch gram_padded(n), n <= MAX_ROWS; rows
-    nw..n-1 basis-only): for ``start="krum"`` k_krum_select writes the start into the weights buffer, then
-    k_cclip_select iterates in place. ``tau <= 0``: from the data. Every buffer comes from ``ws``
-    (capture-safe)."""
-    w = ws.get("weights", n)
-    a0 = None
-    if isinstance(start, torch.Tensor):
-        a0 = ws.get("cclip_a0", n)
-        a0.copy_(start.reshape(-1))
-    elif start == "center":   # all the start weight on the appended centre row
-        a0 = ws.tensors.get("cclip_center")
-        if a0 is None:
-            a0 = ws.tensors["cclip_center"] = _one_hot_last(n, g.device)
-    elif start == "krum":
-        C.gpu_krum_select(g, n, f, m, w, ws.get("order", n, torch.int32), ws.get("scores", n))
-        a0 = w
-    C.gpu_cclip_select(g, n, nw, a0, tau, f, iters, w, ws.get("cclip_dists", n))
-    return w
-
-
-def _one_hot_last(n: int, device) -> torch.Tensor:
-    e = torch.zeros(n, dtype=torch.float32, device=device)
-    e[-1] = 1.0
-    return e
-
-
-def cclip_weights_from_distances(C, D: torch.Tensor, nw: int, f: int, tau: float, iters: int, start="mean",
-                                 m: int | None = None) -> torch.Tensor:
-    """Centered-clipping weights [n] (fp32, CPU) from squared distances: the C++ path, else the oracle.
-    ``tau <= 0``: from the data."""
-    a0 = None
-    if isinstance(start, str) and start == "center":
-        start = _one_hot_last(D.shape[0], "cpu")
-    if isinstance(start, torch.Tensor):
-        a0 = start.reshape(-1).double().cpu()
-    elif start == "krum":
-        a0 = (C.cpu_krum_weights(D, f, m)[0] if C is not None else ref.krum_weights(D, f, m)).double()
-    if C is None:
-        return ref.cclip_weights(D, nw, a0, tau if tau > 0 else None, f, iters).float()
-    return C.cpu_cclip_weights(D, nw, a0, tau, f, iters)
 
 
 def _with_center(rows: Rows, center: torch.Tensor) -> Rows:
@@ -537,39 +421,18 @@ def _with_center(rows: Rows, center: torch.Tensor) -> Rows:
     return out
 
 
-def _cclip_w(rows: Rows, nw: int, f: int, tau: float, iters: int, start, m: int | None) -> torch.Tensor:
-    n = rows.n
-    if n > MAX_ROWS:   # the Gram's own device: large_gram on the GPU, no host round trip
-        g = _large_gram(rows)
-        a0 = start if isinstance(start, torch.Tensor) else None
-        if isinstance(start, str) and start == "center":
-            a0 = _one_hot_last(n, g.device)
-        elif isinstance(start, str) and start == "krum":
-            a0 = large_select(g, f, m) if g.is_cuda else krum_weights_from_gram(g, f, m)
-        return cclip_weights_from_gram(g, nw, a0, tau if tau > 0 else None, f, iters)
-    C = _C_for(rows)
-    if rows.device.type == "cuda":
-        ws = workspace(rows)
-        return cclip_select(C, ws, _gram_into(C, rows, ws), n, nw, f, tau, iters, start, m)
-    D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
-    return cclip_weights_from_distances(C, D, nw, f, tau, iters, start, m)
-
-
 def _cclip_rows_w(gradients, f, tau, iters, start, center, m, pre) -> tuple:
     rows = prepare(gradients)
-    if center is not None:
-        if start is not None:
-            raise ValueError("cclip: give either center or start, not both")
-        if pre is not None:
-            raise ValueError("cclip: a center is not supported under nearest-neighbour mixing")
-        tau_, iters, m = _cclip_args(rows.n, f, tau, iters, "mean", m)
-        rows = _with_center(rows, center)
-        return rows, _cclip_w(rows, rows.n - 1, f, tau_, iters, "center", m)
-    start = "mean" if start is None else start
+    kw = {"tau": tau, "iters": iters, "start": start}
+    if center is None:
+        return rows, selection_weights(rows, resolve("cclip", rows.n, f, m, pre, kw))
+    if start is not None:
+        raise ValueError("cclip: give either center or start, not both")
     if pre is not None:
-        return rows, _nnm_w(rows, f, "cclip", _pre=pre, m=m, iters=iters, tau=tau, start=start)
-    tau_, iters, m = _cclip_args(rows.n, f, tau, iters, start, m)
-    return rows, _cclip_w(rows, rows.n, f, tau_, iters, start, m)
+        raise ValueError("cclip: a center is not supported under nearest-neighbour mixing")
+    sel = resolve("cclip", rows.n, f, m, None, kw)   # the centre is row n, basis-only, and carries the start weight
+    rows = _with_center(rows, center)
+    return rows, selection_weights(rows, replace(sel, n=rows.n, start="center"))
 
 
 def cclip_weights(gradients, f: int = 0, tau: float | None = None, iters: int = 3, start=None, center=None,
@@ -595,142 +458,6 @@ def cclip(gradients, f: int = 0, tau: float | None = None, iters: int = 3, start
 # n - f nearest rows, itself included, before the rule runs. Mixing is linear: the mixed rows' distances
 # follow from the Gram, the rule's weights fold back onto the original rows, and the combine kernels
 # consume those: no pass over the d-length rows, no [n, d] buffer of mixed gradients.
-
-NNM_RULES = ("krum", "geomed", "cclip", "average")
-
-
-def _nnm_args(n: int, f: int, rule: str, pre: str = "nnm", m: int | None = None, iters: int = 32,
-              nu: float = 1e-6) -> tuple:
-    if pre != "nnm":
-        raise ValueError(f"unknown pre-aggregation {pre!r}; available: 'nnm'")
-    if rule not in NNM_RULES:
-        raise ValueError(f"nnm: unsupported rule {rule!r}; available: {NNM_RULES}")
-    if not 0 <= f < n:
-        raise ValueError(f"nnm: expected 0 <= f < n, got f = {f}, n = {n}")
-    if rule == "krum":
-        m = n - f - 2 if m is None else m
-        if n < 2 * f + 3 or not 1 <= m <= n - f - 2:   # Krum's own requirement, as on every other path
-            raise ValueError(f"nnm-krum: expected n >= 2f + 3 and 1 <= m <= n - f - 2, got n = {n}, f = {f}, m = {m}")
-    return m, int(iters), float(nu)
-
-
-def nnm_select(C, ws: Workspace, g: torch.Tensor, n: int, f: int, rule: str, m: int | None = None, iters: int = 32,
-               nu: float = 1e-6, cclip: tuple | None = None) -> torch.Tensor:
-    """Row weights [n] of ``rule`` after the mixing, from a device Gram ``g`` (pitch gram_padded(n),
-    n <= MAX_ROWS): k_nnm_mix -> the rule's own selection on the pseudo-Gram -> k_nnm_unmix. Every
-    buffer comes from ``ws`` (capture-safe). ``cclip``: centered clipping's (tau, iters, start) of
-    :func:`_cclip_args`, the start computed on the mixed rows."""
-    np_ = C.gram_padded(n)
-    H = ws.get("nnm_H", np_ * np_)
-    masks = ws.get("nnm_masks", 2 * n, torch.int64)
-    C.gpu_nnm_mix(g, n, f, H, masks)
-    if rule == "krum":
-        a = ws.get("weights", n)
-        C.gpu_krum_select(H, n, f, m, a, ws.get("order", n, torch.int32), ws.get("scores", n))
-    elif rule == "geomed":
-        a = ws.get("weights", n)
-        C.gpu_geomed_select(H, n, iters, nu, a, ws.get("geomed_dists", n))
-    elif rule == "cclip":
-        a = cclip_select(C, ws, H, n, n, f, cclip[0], cclip[1], cclip[2], m)
-    else:
-        a = ws.tensors.get("avg_w")
-        if a is None:
-            a = torch.full((n,), 1.0 / n, dtype=torch.float32, device=g.device)
-            ws.tensors["avg_w"] = a
-    w = ws.get("nnm_w", n)
-    C.gpu_nnm_unmix(a, masks, n, f, w)
-    return w
-
-
-def nnm_from_gram(g: torch.Tensor, f: int) -> tuple:
-    """(H, S) from a Gram matrix, vectorised in fp64 on g's device (any n, no host round trip): the
-    fp32 pseudo-Gram H of the mixed rows (H_ii = 0, H_ij = -D'_ij / 2, so that distances_from_gram(H)
-    = D') and the membership matrix S [n, n] (bool, S_ij: j ∈ S_i). reference.nnm_distances with
-    matrix products for the sums; equal sets give an exact zero."""
-    n = g.shape[0]
-    c = n - f
-    D = distances_from_gram(g).double()
-    key = D.clone()
-    key.fill_diagonal_(-1.0)   # row i itself first, then (distance, index)
-    near = torch.sort(key, dim=1, stable=True).indices[:, :c]
-    S = torch.zeros((n, n), dtype=torch.bool, device=g.device)
-    S.scatter_(1, near, torch.ones_like(near, dtype=torch.bool))
-    Sd = S.double()
-    D.fill_diagonal_(0.0)
-    fin = torch.isfinite(D)
-    M = Sd @ torch.where(fin, D, torch.zeros_like(D)) @ Sd.T / float(c * c)
-    M = torch.triu(M) + torch.triu(M, 1).T
-    bad = (Sd @ (~fin).double() @ Sd.T) > 0    # an infinite pair inside S_i x S_j
-    taint = torch.diagonal(bad)
-    dm = torch.diagonal(M)
-    Dm = (M - 0.5 * dm[:, None] - 0.5 * dm[None, :]).clamp(min=0)
-    Dm = torch.where((Sd @ Sd.T) == c, torch.zeros_like(Dm), Dm)
-    Dm = torch.where(bad | bad.T | taint[:, None] | taint[None, :], torch.full_like(Dm, math.inf), Dm)
-    H = (-0.5 * Dm).float()
-    H.fill_diagonal_(0.0)
-    return H, S
-
-
-def _nnm_fold(S: torch.Tensor, a: torch.Tensor, c: int) -> torch.Tensor:
-    """w_j = (1/c) Σ_{i : j∈S_i} a_i / Σ_i a_i in fp64 (zero a_i add nothing), as fp32."""
-    a = a.to(S.device, torch.float64)
-    acc = torch.where(S, a[:, None], torch.zeros((), dtype=torch.float64, device=S.device)).sum(0)
-    return (acc / a.sum().clamp(min=torch.finfo(torch.float64).tiny) / c).float()
-
-
-def _nnm_w(rows: Rows, f: int, rule: str, _pre: str = "nnm", tau=None, start="mean", **kw) -> torch.Tensor:
-    n = rows.n
-    cc = None
-    if rule == "cclip":
-        kw.setdefault("iters", 3)
-        if not isinstance(start, str):
-            raise ValueError(f"nnm-cclip: start must be one of {CCLIP_STARTS}")
-    m, iters, nu = _nnm_args(n, f, rule, _pre, **kw)
-    if rule == "cclip":
-        tau_, iters, m = _cclip_args(n, f, tau, iters, start, m)
-        cc = (tau_, iters, start)
-    if n > MAX_ROWS:
-        H, S = nnm_from_gram(_large_gram(rows), f)
-        if rule == "krum":
-            a = large_select(H, f, m) if H.is_cuda else krum_weights_from_gram(H, f, m)
-        elif rule == "geomed":
-            a = geomed_weights_from_gram(H, iters, nu)
-        elif rule == "cclip":
-            a0 = None
-            if start == "krum":
-                a0 = large_select(H, f, m) if H.is_cuda else krum_weights_from_gram(H, f, m)
-            a = cclip_weights_from_gram(H, n, a0, tau, f, iters)
-        else:
-            a = torch.full((n,), 1.0 / n, dtype=torch.float32, device=H.device)
-        return _nnm_fold(S, a, n - f)
-    C = _C_for(rows)
-    if rows.device.type == "cuda":
-        ws = workspace(rows)
-        return nnm_select(C, ws, _gram_into(C, rows, ws), n, f, rule, m, iters, nu, cc)
-    D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
-    return nnm_weights_from_distances(C, D, f, rule, m, iters, nu, cc)
-
-
-def nnm_weights_from_distances(C, D: torch.Tensor, f: int, rule: str, m: int | None = None, iters: int = 32,
-                               nu: float = 1e-6, cclip: tuple | None = None) -> torch.Tensor:
-    """Row weights [n] (fp32, CPU) of ``rule`` after the mixing, from squared distances: the C++ path
-    (n <= MAX_ROWS: the sets are two mask words), else the oracle. ``cclip`` as in :func:`nnm_select`."""
-    n = D.shape[0]
-    if C is None or n > MAX_ROWS:
-        if rule == "cclip":
-            return ref.nnm_weights(D, f, rule, m=m, iters=cclip[1], tau=cclip[0] if cclip[0] > 0 else None,
-                                   start=cclip[2])
-        return ref.nnm_weights(D, f, rule, m=m, iters=iters, nu=nu)
-    Dm, masks = C.cpu_nnm_mix(D, f)
-    if rule == "krum":
-        a = C.cpu_krum_weights(Dm, f, m)[0]
-    elif rule == "geomed":
-        a = C.cpu_geomed_weights(Dm, iters, nu)
-    elif rule == "cclip":
-        a = cclip_weights_from_distances(C, Dm, n, f, cclip[0], cclip[1], cclip[2], m)
-    else:
-        a = torch.full((n,), 1.0 / n, dtype=torch.float32)
-    return C.cpu_nnm_unmix(a, masks, n - f)
 
 
 def nnm_mix(gradients, f: int) -> tuple:
@@ -770,13 +497,14 @@ def masks_from_sets(sets) -> torch.Tensor:
 def nnm_weights(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
     """Weights over the ORIGINAL rows ([n] fp32 on the gradients' device) of ``rule`` (krum: ``m``;
     geomed: ``iters``, ``nu``; cclip: ``tau``, ``iters``, ``start`` "mean" / "krum", ``m``; average) applied to the rows mixed over their n - f nearest."""
-    return _nnm_w(prepare(gradients), f, rule, **kw)
+    rows = prepare(gradients)
+    return selection_weights(rows, resolve(rule, rows.n, f, kw.pop("m", None), "nnm", kw))
 
 
 def nnm(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
     """``rule`` after nearest-neighbour mixing: Σ_j w_j g_j with the weights of :func:`nnm_weights`."""
     rows = prepare(gradients)
-    return _combine_rows(rows, _nnm_w(rows, f, rule, **kw))
+    return _combine_rows(rows, nnm_weights(rows, f, rule, **kw))
 
 
 # NNM before a coordinate-wise rule (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing before a
@@ -874,27 +602,7 @@ def nnm_coord(gradients, f: int, rule: str = "trimmed-mean") -> torch.Tensor:
 
 def bulyan_weights(gradients, f: int, m: int | None = None) -> torch.Tensor:
     rows = prepare(gradients)
-    m = rows.n - f - 2 if m is None else m
-    return _bulyan_W(rows, f, m)
-
-
-def _bulyan_W(rows: Rows, f: int, m: int) -> torch.Tensor:
-    t = rows.n - 2 * f - 2
-    C = _C_for(rows)
-    if rows.device.type == "cuda" and rows.n <= MAX_ROWS:
-        ws = workspace(rows)
-        g = _gram_into(C, rows, ws)
-        W = ws.get("bulyan_W", t * rows.n)
-        C.gpu_bulyan_select(g, rows.n, f, m, t, W)
-        return W.view(t, rows.n)
-    if rows.device.type == "cuda" and rows.n > MAX_ROWS:
-        return large_select(_large_gram(rows), f, m, bulyan=True)
-    D = pairwise_distances(rows.obj) if C is not None else ref.pairwise_sqdist(rows.stacked())
-    if rows.n > MAX_ROWS:
-        return _large_bulyan_weights(D, f, m).float().to(rows.device)
-    if C is None:
-        return ref.bulyan_weights(D, f, m).float().to(rows.device)
-    return C.cpu_bulyan_weights(D, f, m, t)
+    return selection_weights(rows, resolve("bulyan", rows.n, f, m))
 
 
 def bulyan(gradients, f: int, m: int | None = None, **_) -> torch.Tensor:
@@ -902,7 +610,7 @@ def bulyan(gradients, f: int, m: int | None = None, **_) -> torch.Tensor:
     m = rows.n - f - 2 if m is None else m
     t = rows.n - 2 * f - 2
     beta = t - 2 * f
-    W = _bulyan_W(rows, f, m)
+    W = bulyan_weights(rows, f, m)
     if _large(rows):   # V = W·X column chunk by chunk (bounded fp32 memory), then the radix-select tail
         X, Wd = _matrix(rows), W.to(rows.device, torch.float32)
         out = torch.empty(rows.d, dtype=torch.float32, device=rows.device)
@@ -975,35 +683,12 @@ def condense(gradients, p: float = 0.9, seed: int | None = None, **_) -> torch.T
 
 def brute_weights(gradients, f: int) -> torch.Tensor:
     rows = prepare(gradients)
-    return _brute_w(rows, f)
-
-
-BRUTE_MAX_SUBSETS = 2 ** 32
-
-
-def _brute_w(rows: Rows, f: int) -> torch.Tensor:
-    # the device search keys each subset by its 32-bit rank (gar_gram.hip k_brute_*): refuse
-    # what it cannot index (C(64, 56) is 4.4e9 subsets: infeasible on any device anyway)
-    subsets = math.comb(rows.n, rows.n - f) if 0 <= f <= rows.n else 0
-    if subsets > BRUTE_MAX_SUBSETS:
-        raise ValueError(f"brute: C({rows.n}, {rows.n - f}) = {subsets} subsets exceeds 2^32; use a smaller f "
-                         "or another rule")
-    C = _C_for(rows)
-    if rows.device.type == "cuda" and rows.n <= 64:
-        ws = workspace(rows)
-        g = _gram_into(C, rows, ws)
-        best = ws.get("brute_best", 1, torch.int64)
-        w = ws.get("weights", rows.n)
-        C.gpu_brute_select(g, rows.n, f, best, w)
-        return w
-    if C is None or rows.n > 64:
-        return ref.brute_weights(pairwise_distances(rows.obj) if C else ref.pairwise_sqdist(rows.stacked()), f).float().to(rows.device)
-    return C.cpu_brute_weights(C.cpu_pairwise(rows.obj), f)
+    return selection_weights(rows, resolve("brute", rows.n, f))
 
 
 def brute(gradients, f: int, **_) -> torch.Tensor:
     rows = prepare(gradients)
-    return _combine_rows(rows, _brute_w(rows, f))
+    return _combine_rows(rows, brute_weights(rows, f))
 
 
 def aksel_weights(gradients, f: int, mode: str = "mid") -> torch.Tensor:
@@ -1077,187 +762,6 @@ def _large_gram(rows: Rows) -> torch.Tensor:
         return large_gram(_matrix(rows))
     X = rows.stacked().float()
     return X @ X.T
-
-
-def _large_krum_weights(rows: Rows, f: int, m: int) -> torch.Tensor:
-    g = _large_gram(rows)
-    if g.is_cuda:
-        return large_select(g, f, m)
-    return krum_weights_from_gram(g, f, m)
-
-
-def large_select(g: torch.Tensor, f: int, m: int, bulyan: bool = False) -> torch.Tensor:
-    """Multi-Krum weights [n] (or Bulyan's W [t, n]) from a GPU fp32 Gram of up to LARGE_ROWS rows, on
-    device (gar_large.hip: per-row neighbourhoods by an LDS bitonic sort, the selection rounds in one
-    workgroup; fp64 distances): no host round trip."""
-    n = g.shape[0]
-    rounds = n - 2 * f - 2 if bulyan else 1
-    W = torch.empty((rounds, n), dtype=torch.float32, device=g.device)
-    _native.native().gpu_large_select(g.float().contiguous(), f, m, rounds, bulyan, W)
-    return W if bulyan else W[0]
-
-
-def distances_from_gram(g: torch.Tensor) -> torch.Tensor:
-    """Squared distances [n, n] from a Gram matrix: +inf on the diagonal and where non-finite."""
-    dg = torch.diagonal(g)
-    D = (dg[:, None] + dg[None, :] - 2 * g)
-    D = torch.where(torch.isfinite(D), D.clamp(min=0), torch.full_like(D, math.inf))
-    D.fill_diagonal_(math.inf)
-    return D
-
-
-def krum_weights_from_gram(g: torch.Tensor, f: int, m: int) -> torch.Tensor:
-    """Multi-Krum weights [n] (fp32, g's device) from a Gram matrix (vectorised, any n)."""
-    n = g.shape[0]
-    D = distances_from_gram(g)
-    q = n - f - 2
-    near = torch.sort(D, dim=1, stable=True).values[:, :q]
-    scores = near.sum(1)
-    scores = torch.where(torch.isnan(scores), torch.full_like(scores, math.inf), scores)
-    order = torch.sort(scores, stable=True).indices
-    w = torch.zeros(n, dtype=torch.float32, device=g.device)
-    w[order[:m]] = 1.0 / m
-    return w
-
-
-def geomed_weights_from_gram(g: torch.Tensor, iters: int = 32, nu: float = 1e-6) -> torch.Tensor:
-    """Geometric-median weights [n] (fp32, g's device) from a Gram matrix (vectorised, any n):
-    reference.geomed_weights with the distances built as the selection kernels build them."""
-    n = g.shape[0]
-    D = distances_from_gram(g).double()
-    D.fill_diagonal_(0.0)
-    fin = torch.isfinite(D)
-    fin.fill_diagonal_(False)
-    valid = fin.any(1)
-    D = torch.where(fin, D, torch.zeros_like(D))
-    nv = valid.sum()
-    # no valid row (n == 1, every pair non-finite): uniform 1/n, without a host branch on device data
-    a = torch.where(valid, 1.0 / nv.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=g.device))
-    for _ in range(iters):
-        s = (D * a[None, :]).sum(1)
-        q = 0.5 * (a * s).sum()
-        b = torch.where(valid, 1.0 / (s - q).clamp(min=0).sqrt().clamp(min=nu), torch.zeros_like(s))
-        a = b / b.sum().clamp(min=torch.finfo(torch.float64).tiny)
-    a = torch.where(nv > 0, a, torch.full_like(a, 1.0 / n))
-    return a.float()
-
-
-def dnc_weights_from_gram(g: torch.Tensor, m: int, iters: int = 16, with_scores: bool = False):
-    """DnC weights [n] (fp32, g's device; with the fp32 scores when ``with_scores``) from a Gram matrix
-    (vectorised in fp64, any n, no host round trip): reference.dnc_weights with the distances built as
-    the selection kernels build them, and rank masks in place of a host-side kv."""
-    n = g.shape[0]
-    dev = g.device
-    D = distances_from_gram(g).double()
-    D.fill_diagonal_(0.0)
-    fin = torch.isfinite(D)
-    fin.fill_diagonal_(False)
-    valid = fin.any(1)
-    D = torch.where(fin, D, torch.zeros_like(D))   # invalid rows and columns: all zero
-    zero = torch.zeros((), dtype=torch.float64, device=dev)
-    nv = valid.sum()
-    nvd = nv.clamp(min=1).double()
-    ids = torch.arange(n, device=dev)
-    r = D.sum(1) / nvd
-    gm = r.sum() / nvd
-    kappa = torch.where(valid, r - 0.5 * gm, torch.full_like(r, -math.inf))
-    star = torch.where(kappa == kappa.max(), ids, torch.full_like(ids, n - 1)).min().reshape(1)
-    b = torch.where(valid, -0.5 * (D.index_select(1, star)[:, 0] - r - r.index_select(0, star) + gm), zero)
-    u = torch.zeros_like(b)
-    tiny = torch.finfo(torch.float64).tiny
-    for _ in range(iters):
-        nu = (b * b).sum().sqrt()
-        u = torch.where(nu > 0, b / nu.clamp(min=tiny), zero)
-        c = u.sum() / nvd
-        t = (D * torch.where(valid, u - c, zero)[None, :]).sum(1)
-        b = torch.where(valid, -0.5 * (t - t.sum() / nvd), zero)
-    lam = (u * b).sum()
-    s = torch.where(lam > 0, b * b / lam.clamp(min=tiny), zero).float()
-    s = torch.where(valid, s, torch.full_like(s, math.inf))
-    # rank by (fp32 score, index); invalid rows carry +inf and kv <= |V| keeps them out
-    before = (s[None, :] < s[:, None]) | ((s[None, :] == s[:, None]) & (ids[None, :] < ids[:, None]))
-    kv = nv.clamp(max=m)
-    keep = valid & (before.sum(1) < kv)
-    w = torch.where(keep, 1.0 / kv.clamp(min=1).double(), zero).float()
-    # no valid row (n == 1, every pair non-finite): uniform 1/n and zero scores, without a host branch
-    w = torch.where(nv > 0, w, torch.full_like(w, 1.0 / n))
-    s = torch.where(nv > 0, s, torch.zeros_like(s))
-    return (w, s) if with_scores else w
-
-
-def cclip_weights_from_gram(g: torch.Tensor, nw: int | None = None, a0: torch.Tensor | None = None,
-                            tau: float | None = None, f: int = 0, iters: int = 3) -> torch.Tensor:
-    """Centered-clipping weights [n] (fp32, g's device) from a Gram matrix (vectorised in fp64, any n, no
-    host round trip): reference.cclip_weights with the distances built as the selection kernels build
-    them. Rows nw..n-1 are basis-only; ``a0`` None: uniform on the workers; ``tau`` None: from the data."""
-    n = g.shape[0]
-    nw = n if nw is None else nw
-    D = distances_from_gram(g).double()
-    D.fill_diagonal_(0.0)
-    fin = torch.isfinite(D)
-    fin.fill_diagonal_(False)
-    valid = fin.any(1)
-    D = torch.where(fin, D, torch.zeros_like(D))
-    zero = torch.zeros((), dtype=torch.float64, device=g.device)
-    is_worker = torch.arange(n, device=g.device) < nw
-    V = valid & is_worker
-    nv = V.sum()
-    nvd = nv.clamp(min=1).double()
-    uniform = torch.where(V, 1.0 / nvd, zero)
-    if a0 is None:
-        a = uniform
-    else:
-        a = torch.where(valid, a0.to(g.device, torch.float64).reshape(-1), zero)
-        tot = a.sum()
-        ok = torch.isfinite(tot) & (tot > 0)
-        a = torch.where(ok, a / torch.where(ok, tot, torch.ones_like(tot)), uniform)
-    k = (nv - f).clamp(min=1)
-    for _ in range(iters):
-        s = (D * a[None, :]).sum(1)
-        q = 0.5 * (a * s).sum()
-        r = (s - q).clamp(min=0).sqrt()
-        if tau is None:   # the k-th smallest r over V: only its value is used
-            t = torch.sort(torch.where(V, r, torch.full_like(r, math.inf))).values.gather(0, (k - 1).reshape(1))[0]
-        else:
-            t = torch.full((), float(tau), dtype=torch.float64, device=g.device)
-        lam = torch.where(V & (r > t), t / r, V.double())
-        a = a * (1.0 - lam.sum() / nvd) + lam / nvd
-    # no valid worker (n == 1, every pair non-finite): uniform on the workers, without a host branch on device data
-    a = torch.where(nv > 0, a, torch.where(is_worker, 1.0 / nw, zero))
-    return a.float()
-
-
-def _stable_order(v: torch.Tensor) -> torch.Tensor:
-    """Indices by (value, index), NaN last: reference._order."""
-    return torch.sort(_nan_inf(v), stable=True).indices
-
-
-def _large_bulyan_weights(D: torch.Tensor, f: int, m: int) -> torch.Tensor:
-    """reference.bulyan_weights vectorised over n (fp64, CPU: t sequential tiny steps):
-    each gradient's q nearest-neighbour distances P, scores = row sums, then t rounds of
-    'weights over the mk best scores; remove the best; subtract its column of P'."""
-    D = D.double().cpu()
-    n = D.shape[0]
-    t, q = n - 2 * f - 2, n - f - 2
-    Dn = _nan_inf(D.clone())
-    Dn.fill_diagonal_(math.inf)
-    near = torch.sort(Dn, dim=1, stable=True).indices[:, :q]
-    P = torch.zeros((n, n), dtype=torch.float64)
-    P.scatter_(1, near, D.gather(1, near))
-    scores = P.sum(1)
-    W = torch.zeros((t, n), dtype=torch.float64)
-    for k in range(t):
-        mk = max(m - k, 1)
-        order = _stable_order(scores)
-        W[k, order[:mk]] = 1.0 / mk
-        best = int(order[0])
-        scores -= P[:, best]
-        scores[best] = ref.FLT_MAX
-    return W
-
-
-def _nan_inf(X: torch.Tensor) -> torch.Tensor:
-    return torch.where(torch.isnan(X), torch.full_like(X, math.inf), X)
 
 
 def _torch_closest_mean(V: torch.Tensor, beta: int) -> torch.Tensor:

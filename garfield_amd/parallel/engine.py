@@ -35,7 +35,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from garfield_amd import _native
-from garfield_amd.ops import gar
+from garfield_amd.ops import gar, selection
 from garfield_amd.parallel.comm import DistContext, all_gather_rows, collectives_on
 from garfield_amd.runtime.attacks import NEEDS_ESTIMATES, apply_attack
 from garfield_amd.utils.flat import FlatParams
@@ -49,13 +49,15 @@ from garfield_amd.utils.profiling import PhaseTimer
 # the first convolution; users may override the variable explicitly.
 os.environ.setdefault("MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_WRW_XDLOPS", "0")
 
-WEIGHTED_RULES = {"average", "krum", "brute", "aksel", "geomed", "cclip", "dnc"}
+# rules that end in one weight vector over the rows: the selection table's (Bulyan ends in W [t, n] and a
+# coordinate-wise tail), the average and Aksel
+WEIGHTED_RULES = (set(selection.TABLE) - {"bulyan"}) | {"average", "aksel"}
 _LP_MODULES = (nn.modules.conv._ConvNd, nn.Linear)
 COORD_RULES = {"median", "trimmed-mean", "averaged-median", "average-nan", "condense", "bulyan"}
 # coordinate-wise rules accepted behind pre_aggregation="nnm" (gar.nnm_coord; "nnm-median" exists through
 # the functional interface and the registry only)
 NNM_ENGINE_COORD_RULES = ("trimmed-mean",)
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip", "dnc"}   # per-layer != flat only for distance-based rules
+LAYERWISE_RULES = set(selection.TABLE) | {"aksel"}   # per-layer != flat only for distance-based rules
 # Layer-wise Krum as device operations (gar_layerwise.hip: one segmented Gram launch, a batched
 # selection, one segmented combine + SGD); "0" runs the per-segment loop (the reference form).
 LW_DEVICE = os.environ.get("GARFIELD_LW_DEVICE", "1") != "0"
@@ -264,6 +266,7 @@ class RobustDataParallel:
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(cfg.seed + 7919 * self.rank)
         self._check_gar()
+        self._sel = self._selection(self.n)   # resolved once: no argument handling per step
         self.timer = PhaseTimer(self.device, cfg.profile_phases)
         self._graph = None
         self._graph_failed = False
@@ -447,16 +450,13 @@ class RobustDataParallel:
             raise ValueError(f"pre_aggregation='nnm' is not yet supported by the sharded aggregation of more than "
                              f"{gar.MAX_ROWS} rows (shard_gar=False runs the unsharded path)")
 
-    def _nnm_kwargs(self, kw: dict) -> dict:
-        """The rule's keyword arguments of gar.nnm_weights."""
-        if self.cfg.gar == "krum":
-            return {"m": self.cfg.m}
-        if self.cfg.gar == "geomed":
-            iters, nu = self._geomed_args(kw)
-            return {"iters": iters, "nu": nu}
-        if self.cfg.gar == "cclip":
-            return self._cclip_kwargs(kw)
-        return {}
+    def _selection(self, n: int):
+        """The configured rule's resolved selection over ``n`` rows (ops/selection.py); None for a rule that
+        is not a distance-based selection (coordinate-wise, the plain average, Aksel)."""
+        cfg = self.cfg
+        if cfg.gar in selection.TABLE or (cfg.pre_aggregation and cfg.gar in gar.NNM_RULES):
+            return selection.resolve(cfg.gar, n, cfg.f, cfg.m, cfg.pre_aggregation, cfg.gar_kwargs)
+        return None
 
     def _check_gar(self) -> None:
         from garfield_amd import aggregators
@@ -540,16 +540,16 @@ class RobustDataParallel:
         rule = cfg.gar
         kw = dict(cfg.gar_kwargs)
         if cfg.layerwise and rule in LAYERWISE_RULES:
-            self._layerwise_update(rule, kw, first)
+            self._layerwise_update(rule, first)
             self.step_count += 1
             return
         if self.device.type == "cuda" and self.n > gar.MAX_ROWS:
-            self._large_update(rule, kw, first)
+            self._large_update(rule, first)
         elif self.device.type == "cuda":
             C = self._C
             param, mom = self.flat.data[: self.d], self.mom[: self.d]
             if rule in WEIGHTED_RULES:
-                w = self._weights(rule, kw)
+                w = self._weights()
                 self.last_weights = w
                 C.gpu_combine_sgd(self.G, w, param, mom, None, self._shadow, cfg.lr, cfg.momentum, cfg.dampening,
                                   cfg.weight_decay, cfg.nesterov, first)
@@ -559,32 +559,25 @@ class RobustDataParallel:
                 C.gpu_combine_sgd(self._gagg.view(1, self.ld)[:, : self.d], self._one, param, mom, None, self._shadow,
                                   cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
         else:
-            gkw = dict(kw)
-            if rule not in ("average", "median", "average-nan"):
-                gkw["f"] = cfg.f
-            if cfg.m is not None and rule in ("krum", "bulyan", "dnc"):
-                gkw["m"] = cfg.m
-            if rule == "condense":
-                gkw.setdefault("seed", cfg.seed + self.step_count)
             if cfg.pre_aggregation and rule in NNM_ENGINE_COORD_RULES:   # no weights: the rule over the set means
                 self.last_weights = None
                 g = gar.nnm_coord(self.G.float(), cfg.f, rule).float()
-            elif rule in ("geomed", "cclip", "dnc") or cfg.pre_aggregation:   # kept for last_weights, then the rule's own combine
-                self.last_weights = w = self._weights(rule, kw, self.G.float())
+            elif self._sel is not None and rule in WEIGHTED_RULES:   # kept for last_weights, then the rule's own combine
+                self.last_weights = w = self._weights(self.G.float())
                 g = gar.combine(self.G.float(), w).float()
             else:
-                g = gar.aggregate(rule, self.G.float(), **gkw).float()
+                g = gar.aggregate(rule, self.G.float(), **self._rule_kwargs()).float()
             self._sgd_cpu(g, first)
         self.step_count += 1
 
-    def _large_update(self, rule: str, kw: dict, first: bool) -> None:
+    def _large_update(self, rule: str, first: bool) -> None:
         """More than MAX_ROWS (128) rows on the GPU (up to LARGE_ROWS = 1024, e.g. Bulyan with
         32 workers per GPU on 8 GPUs): the [n, d] set as one matrix on ``gar_large.hip``
         (compacted-weight combine, radix-select coordinate rules, split-K MFMA Gram for the
         selections), the aggregate rounded to the exchange dtype, then the fused update."""
         cfg = self.cfg
         if rule in WEIGHTED_RULES:
-            w = self._weights(rule, kw)
+            w = self._weights()
             self.last_weights = w
             g = gar.combine(self.G, w)
         else:
@@ -594,22 +587,21 @@ class RobustDataParallel:
                                 self._shadow, cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov,
                                 first)
 
-    def _layerwise_update(self, rule: str, kw: dict, first: bool) -> None:
+    def _layerwise_update(self, rule: str, first: bool) -> None:
         """The GAR on every parameter tensor's slice of the [n, d] rows (each parameter is
         one contiguous segment of the memory-order flat layout), then one update.
 
-        GPU Krum runs as three device launches over all segments (``_layerwise_device``);
-        otherwise a loop over the segments: weighted rules compute each segment's weights and
-        combine it in fp32 (exactly the arithmetic of the device path), other rules aggregate
-        the segment with the rule itself."""
+        On the GPU the table's selections run over all segments at once (``_layerwise_device``: a
+        segmented Gram, one batched selection, a segmented combine or Bulyan tail); Brute has no batched
+        launcher and the segmented Bulyan tail takes up to 64 rows. Otherwise a loop over the segments:
+        weighted rules compute each segment's weights and combine it in fp32 (exactly the arithmetic of
+        the device path), other rules aggregate the segment with the rule itself."""
         cfg = self.cfg
-        gkw = dict(kw, f=cfg.f)
-        if cfg.m is not None and rule in ("krum", "bulyan", "dnc"):
-            gkw["m"] = cfg.m
+        gkw = self._rule_kwargs()
         cuda = self.device.type == "cuda"
-        if cuda and LW_DEVICE and self.n <= gar.MAX_ROWS and (rule in ("krum", "geomed", "cclip", "dnc")
-                                                              or (rule == "bulyan" and self.n <= 64)):
-            self._layerwise_device(rule, first)
+        if (cuda and LW_DEVICE and self._sel is not None and rule != "brute"
+                and self.n <= (64 if rule == "bulyan" else gar.MAX_ROWS)):
+            self._layerwise_device(first)
             return
         g = self._gagg if self._gagg is not None else torch.zeros(self.ld, dtype=torch.float32, device=self.device)
         self._gagg = g
@@ -617,7 +609,7 @@ class RobustDataParallel:
         for off, numel in self._segments():
             seg = self.G[:, off:off + numel]
             if rule in WEIGHTED_RULES:
-                w = self._weights(rule, kw, seg if cuda else seg.float())
+                w = self._weights(seg if cuda else seg.float())
                 ws.append(w.clone())
                 gar.combine_into(seg, w, g[off:off + numel])
             else:
@@ -634,12 +626,13 @@ class RobustDataParallel:
         """(offset, numel) of every parameter segment, by offset."""
         return sorted(zip(self.flat.offsets, self.flat.numels))
 
-    def _layerwise_device(self, rule: str, first: bool) -> None:
-        """Layer-wise Krum / Bulyan on device: per-segment Grams (one launch over a job table + one
-        segmented reduction), every segment's selection in one batched launch, then Krum: one
-        segmented combine fused with the SGD update; Bulyan: one segmented tail launch (each
-        coordinate's t selection means with its segment's W, their averaged median) + the update."""
-        cfg = self.cfg
+    def _layerwise_device(self, first: bool) -> None:
+        """The layer-wise selection on device: per-segment Grams (one launch over a job table + one
+        segmented reduction), every segment's selection batched (``Selection.on_device`` with one batch
+        entry per segment), then one segmented combine fused with the SGD update; Bulyan: one segmented
+        tail launch (each coordinate's t selection means with its segment's W, their averaged median) +
+        the update."""
+        cfg, sel = self.cfg, self._sel
         C = self._C
         lw = getattr(self, "_lw", None)
         if lw is None:
@@ -658,90 +651,40 @@ class RobustDataParallel:
                 seg_off=torch.tensor(offs, dtype=torch.int64, device=dev),
                 slabs=torch.empty(len(jobs) * C.gram_slab_floats(n), dtype=torch.float32, device=dev),
                 gram=torch.empty(L * np_ * np_, dtype=torch.float32, device=dev),
-                w=torch.empty((L, n), dtype=torch.float32, device=dev),
-                order=torch.empty((L, n), dtype=torch.int32, device=dev),
-                scores=torch.empty((L, n), dtype=torch.float32, device=dev),
-                dists=torch.empty((L, n), dtype=torch.float32, device=dev), L=L)
-        n, f = self.n, cfg.f
-        m = cfg.m if cfg.m is not None else n - f - 2
+                ws=gar.Workspace(n, 0, dev), L=L)   # the selection's [L, n] buffers
         G = self.G[:, : self.d]
+        args = (cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
         C.gpu_lw_gram(G, lw["jobs"], lw["seg_lo"], lw["slabs"], lw["gram"])
-        if rule == "bulyan":
-            t = n - 2 * f - 2
-            W = lw.get("W")
-            if W is None:
-                W = lw["W"] = torch.empty((lw["L"], t, n), dtype=torch.float32, device=self.device)
+        w = sel.on_device(C, lw["gram"], lw["ws"], lw["L"])
+        if cfg.gar == "bulyan":
             if self._gagg is None:
                 self._gagg = torch.zeros(self.ld, dtype=torch.float32, device=self.device)
             g = self._gagg[: self.d]
-            C.gpu_bulyan_select(lw["gram"], n, f, m, t, W, lw["L"])
-            C.gpu_lw_bulyan_tail(G, lw["jobs"], W, t, t - 2 * f, g)
+            C.gpu_lw_bulyan_tail(G, lw["jobs"], w.view(lw["L"], sel.t, sel.n), sel.t, sel.t - 2 * sel.f, g)
             C.gpu_combine_sgd(g.view(1, -1), self._one, self.flat.data[: self.d], self.mom[: self.d], None,
-                              self._shadow, cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov,
-                              first)
+                              self._shadow, *args)
             self.last_weights = None
             return
-        if rule == "geomed":
-            iters, nu = self._geomed_args(cfg.gar_kwargs)
-            C.gpu_geomed_select(lw["gram"], n, iters, nu, lw["w"], lw["dists"], lw["L"])
-        elif rule == "cclip":   # every segment's start (Krum's batched selection) and clipping rounds, in place
-            tau, iters, start = self._cclip_args(cfg.gar_kwargs)
-            if start == "krum":
-                C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
-            C.gpu_cclip_select(lw["gram"], n, n, lw["w"] if start == "krum" else None, tau, f, iters, lw["w"],
-                               lw["dists"], lw["L"])
-        elif rule == "dnc":   # every segment's power rounds and selection in one batched launch
-            C.gpu_dnc_select(lw["gram"], n, cfg.m if cfg.m is not None else n - f, self._dnc_iters(cfg.gar_kwargs),
-                             lw["w"], lw["scores"], lw["L"])
-        else:
-            C.gpu_krum_select(lw["gram"], n, f, m, lw["w"], lw["order"], lw["scores"], lw["L"])
-        C.gpu_lw_combine_sgd(G, lw["jobs"], lw["seg_off"], 0, lw["w"], self.flat.data[: self.d], self.mom[: self.d],
-                             self._shadow, cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
-        self.last_weights = lw["w"]
+        self.last_weights = w = w.view(lw["L"], sel.n)
+        C.gpu_lw_combine_sgd(G, lw["jobs"], lw["seg_off"], 0, w, self.flat.data[: self.d], self.mom[: self.d],
+                             self._shadow, *args)
 
-    def _weights(self, rule: str, kw: dict, G=None) -> torch.Tensor:
-        f = self.cfg.f
+    def _weights(self, G=None) -> torch.Tensor:
+        """The configured rule's row weights (Bulyan: W [t, n]) over ``G`` (default: the [n, d] exchange rows)."""
         G = self.G if G is None else G
-        if self.cfg.pre_aggregation:   # the rule on the mixed rows, folded back into row weights
-            return gar.nnm_weights(G, f, rule, **self._nnm_kwargs(kw))
-        if rule == "average":
+        n = len(G)
+        sel = self._sel if n == self.n else self._selection(n)   # an explicit row list may be any subset
+        if sel is not None:
+            return gar.selection_weights(G, sel)
+        if self.cfg.gar == "average":
+            if n != self.n:
+                return torch.full((n,), 1.0 / n, dtype=torch.float32, device=self.device)
             w = getattr(self, "_avg_w", None)
             if w is None:
                 w = torch.full((self.n,), 1.0 / self.n, dtype=torch.float32, device=self.device)
                 self._avg_w = w
             return w
-        if rule == "krum":
-            return gar.krum_weights(G, f, self.cfg.m)
-        if rule == "brute":
-            return gar.brute_weights(G, f)
-        if rule == "geomed":
-            return gar.geomed_weights(G, *self._geomed_args(kw))
-        if rule == "cclip":
-            return gar.cclip_weights(G, f, **self._cclip_kwargs(kw))
-        if rule == "dnc":
-            return gar.dnc_weights(G, f, self.cfg.m, self._dnc_iters(kw))
-        return gar.aksel_weights(G, f, kw.get("mode", "mid"))
-
-    @staticmethod
-    def _geomed_args(kw: dict) -> tuple:
-        """(iters, nu) of the geometric median from the rule's keyword arguments."""
-        return int(kw.get("iters", 32)), float(kw.get("nu", 1e-6))
-
-    @staticmethod
-    def _dnc_iters(kw: dict) -> int:
-        """The power-iteration count of DnC from the rule's keyword arguments (validated at construction)."""
-        return kw.get("iters", 16)
-
-    @staticmethod
-    def _cclip_args(kw: dict) -> tuple:
-        """(tau as the launchers take it: 0 = from the data, iters, start) of centered clipping."""
-        tau = kw.get("tau")
-        return (0.0 if tau is None else float(tau)), int(kw.get("iters", 3)), kw.get("start", "mean")
-
-    def _cclip_kwargs(self, kw: dict) -> dict:
-        """Centered clipping's keyword arguments of gar.cclip_weights / gar.nnm_weights."""
-        return {"tau": kw.get("tau"), "iters": int(kw.get("iters", 3)), "start": kw.get("start", "mean"),
-                "m": self.cfg.m}
+        return gar.aksel_weights(G, self.cfg.f, self.cfg.gar_kwargs.get("mode", "mid"))
 
     def _coordinate(self, rule: str, kw: dict, out: torch.Tensor, G=None) -> None:
         """Coordinate-wise rule (or Bulyan) over ``G`` (default: the [n, d] exchange rows;
@@ -756,7 +699,7 @@ class RobustDataParallel:
             gar.nnm_coord_into(C, ws, rows.obj, gar._gram_into(C, rows, ws), n, f, rule, out)
         elif rule == "bulyan":
             t = n - 2 * f - 2
-            W = gar.bulyan_weights(G, f, self.cfg.m)
+            W = self._weights(G)
             C.gpu_coordwise(G, modes["bulyan-tail"], f, t - 2 * f, W.reshape(-1), t, 0, 1.0, out)
         elif rule == "median":
             C.gpu_coordwise(G, modes["median"], 0, 0, None, 0, 0, 1.0, out)
@@ -783,7 +726,7 @@ class RobustDataParallel:
         kw = dict(cfg.gar_kwargs)
         if cfg.gar not in ("average", "median", "average-nan"):
             kw["f"] = cfg.f
-        if cfg.m is not None and cfg.gar in ("krum", "bulyan", "dnc"):
+        if cfg.m is not None and self._sel is not None:   # the selections' m (of these, Bulyan runs by name)
             kw["m"] = cfg.m
         if cfg.gar == "condense":
             kw.setdefault("seed", cfg.seed + self.step_count)
@@ -798,23 +741,7 @@ class RobustDataParallel:
         if self.device.type == "cuda":
             C = self._C
             if cfg.gar in WEIGHTED_RULES:
-                if cfg.pre_aggregation:
-                    w = gar.nnm_weights(rows, cfg.f, cfg.gar, **self._nnm_kwargs(cfg.gar_kwargs))
-                elif cfg.gar == "krum":
-                    w = gar.krum_weights(rows, cfg.f, cfg.m)
-                elif cfg.gar == "brute":
-                    w = gar.brute_weights(rows, cfg.f)
-                elif cfg.gar == "aksel":
-                    w = gar.aksel_weights(rows, cfg.f, cfg.gar_kwargs.get("mode", "mid"))
-                elif cfg.gar == "geomed":
-                    w = gar.geomed_weights(rows, *self._geomed_args(cfg.gar_kwargs))
-                elif cfg.gar == "cclip":
-                    w = gar.cclip_weights(rows, cfg.f, **self._cclip_kwargs(cfg.gar_kwargs))
-                elif cfg.gar == "dnc":
-                    w = gar.dnc_weights(rows, cfg.f, cfg.m, self._dnc_iters(cfg.gar_kwargs))
-                else:
-                    w = torch.full((len(rows),), 1.0 / len(rows), device=self.device)
-                self.last_weights = w
+                self.last_weights = w = self._weights(rows)
                 C.gpu_combine_sgd(rows, w, param, mom, None, self._shadow, cfg.lr, cfg.momentum, cfg.dampening,
                                   cfg.weight_decay, cfg.nesterov, first)
                 return
@@ -831,8 +758,8 @@ class RobustDataParallel:
             # as a [rows, d] fp32 matrix: the aggregate keeps fp32 (a list of 16-bit rows
             # would round it to the rows' dtype), as the synchronous step's
             X = torch.stack([r.float() for r in rows])
-            if (cfg.pre_aggregation or cfg.gar in ("cclip", "dnc")) and cfg.gar not in NNM_ENGINE_COORD_RULES:
-                self.last_weights = w = self._weights(cfg.gar, dict(cfg.gar_kwargs), X)
+            if cfg.gar in WEIGHTED_RULES and self._sel is not None:
+                self.last_weights = w = self._weights(X)
                 g = gar.combine(X, w).float()
             else:
                 g = gar.aggregate(self._rule_name(), X, **self._rule_kwargs()).float()

@@ -55,14 +55,13 @@ import torch
 import torch.distributed as dist
 
 from garfield_amd import _native
-from garfield_amd.ops import gar
-from garfield_amd.ops import reference as ref
+from garfield_amd.ops import gar, selection
 from garfield_amd.parallel.comm import collectives_on, gloo_backend, world1_collectives
+from garfield_amd.parallel.engine import LAYERWISE_RULES, lw_job_ranges
 from garfield_amd.parallel.rccl import direct_backend
 from garfield_amd.parallel.signals import Handoff
 
-DISTANCE_RULES = {"krum", "brute", "bulyan", "geomed", "cclip", "dnc"}
-LAYERWISE_RULES = {"krum", "bulyan", "brute", "aksel", "geomed", "cclip", "dnc"}
+DISTANCE_RULES = set(selection.TABLE)   # decided from the summed partial Grams / distances
 SUPPORTED = DISTANCE_RULES | {"average", "aksel", "median", "trimmed-mean", "averaged-median", "average-nan",
                               "condense"}
 
@@ -563,7 +562,10 @@ class ShardedAggregator:
                         C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
                     self._update_buckets(mixed)
                     return
-                w = self._select(C, total, rule, f, cfg)
+                if n > e._sel.device_rows:
+                    raise ValueError(f"{rule}: n must be <= {e._sel.device_rows} on the GPU")
+                # after the partial Grams are summed over ranks: the same selection on every rank
+                w = e._sel.on_device(C, total, self._ws_any())
             if rule != "bulyan":
                 e.last_weights = w
 
@@ -572,11 +574,11 @@ class ShardedAggregator:
                     C.gpu_combine_sgd(b.rows, w, p, mom, None, sh, *args)
                 self._update_buckets(combine)
                 return
-            t = n - 2 * f - 2
+            t = e._sel.t
 
             def tail(b):
                 g = self._gagg(b)
-                C.gpu_coordwise(b.rows, modes["bulyan-tail"], f, t - 2 * f, w, t, 0, 1.0, g)
+                C.gpu_coordwise(b.rows, modes["bulyan-tail"], f, t - 2 * f, w.reshape(-1), t, 0, 1.0, g)
                 p, mom, sh = self._param(b)
                 C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
             self._update_buckets(tail)
@@ -634,25 +636,16 @@ class ShardedAggregator:
             mats[b.lo] = self._matrix(b)
         if rule == "brute":   # C(n, f) subsets of n > 128 rows: the device search takes n <= 64
             raise ValueError(f"brute: n must be <= 64 on the GPU (n = {n})")
-        if rule in ("krum", "bulyan", "geomed", "cclip", "dnc"):
+        if rule in DISTANCE_RULES:
             total = None
             for b in self.buckets:
                 g = gar.large_gram(mats[b.lo])                  # MFMA, fp32 (gar_large.hip)
                 total = g if total is None else total.add_(g)
             gs = self._sum_over_ranks(total)[perm][:, perm]          # slot order on every rank
-            m = cfg.m if cfg.m is not None else n - f - 2
-            if rule == "krum":
-                ws = gar.large_select(gs, f, m)
-            elif rule == "geomed":   # vectorised on the Gram's device: no host round trip
-                ws = gar.geomed_weights_from_gram(gs, *e._geomed_args(kw))
-            elif rule == "cclip":
-                ck = e._cclip_kwargs(kw)
-                a0 = gar.large_select(gs, f, m) if ck["start"] == "krum" else None
-                ws = gar.cclip_weights_from_gram(gs, n, a0, ck["tau"], f, ck["iters"])
-            elif rule == "dnc":   # after the partial Grams are summed: the same selection on every rank
-                ws = gar.dnc_weights_from_gram(gs, cfg.m if cfg.m is not None else n - f, e._dnc_iters(kw))
-            else:
-                W = gar.large_select(gs, f, m, bulyan=True)
+            # after the partial Grams are summed: the same selection on every rank, no host round trip
+            ws = e._sel.from_gram(gs)
+            if rule == "bulyan":
+                W = ws
                 Wm = torch.empty_like(W)
                 Wm[:, perm] = W
                 t, beta = n - 2 * f - 2, n - 4 * f - 2
@@ -699,41 +692,6 @@ class ShardedAggregator:
             b.gagg = torch.zeros(b.S, dtype=torch.float32, device=self.e.device)
         return b.gagg
 
-    def _select(self, C, gram_total, rule, f, cfg) -> torch.Tensor:
-        n = self.n
-        ws = self._ws_any()
-        m = cfg.m if cfg.m is not None else n - f - 2
-        if cfg.pre_aggregation:   # after the partial Grams are summed over ranks: the same w on every rank
-            return gar.nnm_select(C, ws, gram_total, n, f, rule, m, *self.e._geomed_args(cfg.gar_kwargs),
-                                  cclip=self.e._cclip_args(cfg.gar_kwargs))
-        if rule == "krum":
-            w = ws.get("weights", n)
-            order = ws.get("order", n, torch.int32)
-            scores = ws.get("scores", n)
-            C.gpu_krum_select(gram_total, n, f, m, w, order, scores)
-            return w
-        if rule == "geomed":
-            w = ws.get("weights", n)
-            dists = ws.get("geomed_dists", n)
-            C.gpu_geomed_select(gram_total, n, *self.e._geomed_args(cfg.gar_kwargs), w, dists)
-            return w
-        if rule == "cclip":
-            return gar.cclip_select(C, ws, gram_total, n, n, f, *self.e._cclip_args(cfg.gar_kwargs), m)
-        if rule == "dnc":
-            return gar.dnc_select(C, ws, gram_total, n, cfg.m if cfg.m is not None else n - f,
-                                  self.e._dnc_iters(cfg.gar_kwargs))
-        if rule == "brute":
-            if n > 64:
-                raise ValueError("brute: n must be <= 64 on the GPU")
-            w = ws.get("weights", n)
-            best = ws.get("brute_best", 1, torch.int64)
-            C.gpu_brute_select(gram_total, n, f, best, w)
-            return w
-        t = n - 2 * f - 2   # bulyan
-        W = ws.get("bulyan_W", t * n)
-        C.gpu_bulyan_select(gram_total, n, f, m, t, W)
-        return W
-
     # ------------------------------------------------------------------ #
     # Layer-wise rules, sharded. Per-parameter-segment squared distances are additive over the
     # coordinate shards too, so each rank adds the partial Grams of its owned coordinates per
@@ -748,8 +706,6 @@ class ShardedAggregator:
         if plan is not None:
             return plan
         e = self.e
-        from garfield_amd.parallel.engine import lw_job_ranges
-
         segs = sorted(zip(e.flat.offsets, e.flat.numels))
         offs = [o for o, _ in segs] + [segs[-1][0] + segs[-1][1]]
         L = len(segs)
@@ -778,12 +734,7 @@ class ShardedAggregator:
                     seg_lo=torch.tensor(seg_lo, dtype=torch.int32, device=dev),
                     slabs=torch.empty(J * C.gram_slab_floats(n), dtype=torch.float32, device=dev),
                     gram=torch.empty(L * np_ * np_, dtype=torch.float32, device=dev))
-            plan["w"] = torch.empty((L, n), dtype=torch.float32, device=dev)
-            plan["order"] = torch.empty((L, n), dtype=torch.int32, device=dev)
-            plan["scores"] = torch.empty((L, n), dtype=torch.float32, device=dev)
-            plan["dists"] = torch.empty((L, n), dtype=torch.float32, device=dev)
-            plan["best"] = torch.empty(1, dtype=torch.int64, device=dev)
-            plan["np"] = np_
+            plan["ws"] = gar.Workspace(n, 0, dev)   # the selection's [L, n] buffers
         self._lwp = plan
         return plan
 
@@ -817,10 +768,9 @@ class ShardedAggregator:
         return torch.zeros((L, n), dtype=torch.float32, device=D.device).scatter_(1, idx, 1.0 / c)
 
     def _layerwise(self, cfg, first: bool) -> None:
-        e = self.e
+        e, sel = self.e, self.e._sel   # sel: None for Aksel (distances to the median, not pairwise)
         rule = cfg.gar
         n, f = self.n, cfg.f
-        m = cfg.m if cfg.m is not None else n - f - 2
         t = n - 2 * f - 2
         plan = self._lw_plan()
         L = plan["L"]
@@ -832,7 +782,8 @@ class ShardedAggregator:
                     for b in self.buckets:
                         self._wait(b)
                         yield b.lo, b.rows
-                plan["w"].copy_(self._lw_aksel_weights(cfg, plan, landed()))
+                w = plan["ws"].get("weights", L * n).view(L, n)
+                w.copy_(self._lw_aksel_weights(cfg, plan, landed()))
             else:
                 total = None
                 for b in self.buckets:          # partial per-segment Grams as the buckets land
@@ -845,11 +796,9 @@ class ShardedAggregator:
                 if total is None:
                     total = torch.zeros_like(next(iter(plan["buckets"].values()))["gram"])
                 total = self._sum_over_ranks(total)
+                w = sel.on_device(C, total, plan["ws"], L)   # every segment's selection, the same on every rank
                 if rule == "bulyan":
-                    W = plan.get("W")
-                    if W is None:
-                        W = plan["W"] = torch.empty((L, t, n), dtype=torch.float32, device=e.device)
-                    C.gpu_bulyan_select(total, n, f, m, t, W, L)
+                    W = w.view(L, t, n)
                     e.last_weights = None
                     for b in self._update_order():
                         bp = plan["buckets"][b.lo]
@@ -860,29 +809,13 @@ class ShardedAggregator:
                         C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
                         self._gather_bucket(b)
                     return
-                if rule == "brute":
-                    np2 = plan["np"] ** 2
-                    for si in range(L):
-                        C.gpu_brute_select(total[si * np2:(si + 1) * np2], n, f, plan["best"], plan["w"][si])
-                elif rule == "geomed":
-                    C.gpu_geomed_select(total, n, *e._geomed_args(cfg.gar_kwargs), plan["w"], plan["dists"], L)
-                elif rule == "cclip":
-                    tau, iters, start = e._cclip_args(cfg.gar_kwargs)
-                    if start == "krum":
-                        C.gpu_krum_select(total, n, f, m, plan["w"], plan["order"], plan["scores"], L)
-                    C.gpu_cclip_select(total, n, n, plan["w"] if start == "krum" else None, tau, f, iters, plan["w"],
-                                       plan["dists"], L)
-                elif rule == "dnc":
-                    C.gpu_dnc_select(total, n, cfg.m if cfg.m is not None else n - f, e._dnc_iters(cfg.gar_kwargs),
-                                     plan["w"], plan["scores"], L)
-                else:
-                    C.gpu_krum_select(total, n, f, m, plan["w"], plan["order"], plan["scores"], L)
-            e.last_weights = plan["w"]
+                w = w.view(L, n)
+            e.last_weights = w
             for b in self._update_order():
                 bp = plan["buckets"][b.lo]
                 if bp["J"]:
                     p, mom, sh = self._param(b)
-                    C.gpu_lw_combine_sgd(b.rows, bp["jobs"][: bp["J"]], plan["seg_off"], b.own.start, plan["w"],
+                    C.gpu_lw_combine_sgd(b.rows, bp["jobs"][: bp["J"]], plan["seg_off"], b.own.start, w,
                                          p, mom, sh, *args)
                 self._gather_bucket(b)
             return
@@ -890,7 +823,7 @@ class ShardedAggregator:
         for b in self.buckets:
             self._wait(b)
         Xs = {b.lo: torch.stack([r.float() for r in b.rows]) for b in self.buckets}   # [n, S] owned shards
-        Cn = _native.require_for(torch.empty(0))
+        Cn = _native.require_for(e.device)
         if rule == "aksel":
             W = self._lw_aksel_weights(cfg, plan, ((b.lo, list(Xs[b.lo])) for b in self.buckets))
         else:
@@ -906,21 +839,7 @@ class ShardedAggregator:
             for si in range(L):
                 Ds = D[si].clamp_min(0)
                 Ds.fill_diagonal_(math.inf)
-                if rule == "krum":
-                    W[si] = ref.krum_weights(Ds, f, m).float()
-                elif rule == "geomed":
-                    ga = e._geomed_args(cfg.gar_kwargs)
-                    W[si] = (Cn.cpu_geomed_weights(Ds, *ga) if Cn is not None else ref.geomed_weights(Ds, *ga)).float()
-                elif rule == "cclip":
-                    W[si] = gar.cclip_weights_from_distances(Cn, Ds, n, f, *e._cclip_args(cfg.gar_kwargs), m)
-                elif rule == "dnc":
-                    W[si] = gar.dnc_weights_from_distances(Cn, Ds, cfg.m if cfg.m is not None else n - f,
-                                                           e._dnc_iters(cfg.gar_kwargs))
-                elif rule == "brute":
-                    W[si] = (Cn.cpu_brute_weights(Ds, f) if Cn is not None else ref.brute_weights(Ds, f)).float()
-                else:
-                    W[si] = (Cn.cpu_bulyan_weights(Ds, f, m, t) if Cn is not None
-                             else ref.bulyan_weights(Ds, f, m)).float().view(t, n)
+                W[si] = sel.on_host(Cn, Ds)
         e.last_weights = None if rule == "bulyan" else W
         for b in self._update_order():
             X = Xs[b.lo]
@@ -970,32 +889,16 @@ class ShardedAggregator:
                 e.last_weights = w
                 return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
             D = self._sum_over_ranks(gar.pairwise_distances(X))
-            m = cfg.m if cfg.m is not None else n - f - 2
             if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:   # the same sets on every rank, no weights
                 e.last_weights = None
                 return gar.nnm_coord_from_distances(C, X, D, f, rule)
-            if cfg.pre_aggregation:   # the mix runs on the summed distances: the same w on every rank
-                w = gar.nnm_weights_from_distances(C, D, f, rule, m, *e._geomed_args(kw), cclip=e._cclip_args(kw))
-                e.last_weights = w
-                return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
+            w = e._sel.on_host(C, D)   # on the summed distances: the same selection on every rank
             if rule == "bulyan":
                 t = n - 2 * f - 2
                 e.last_weights = None
                 if C is not None:
-                    W = C.cpu_bulyan_weights(D, f, m, t)
-                    return C.cpu_coordwise(X, gar._MODE["bulyan-tail"], f, t - 2 * f, W.reshape(-1), t, 0, 1.0)
-                return gar._torch_closest_mean(ref.bulyan_weights(D, f, m).float() @ X, t - 2 * f)
-            if rule == "krum":
-                w = C.cpu_krum_weights(D, f, m)[0] if C is not None else ref.krum_weights(D, f, m).float()
-            elif rule == "geomed":
-                ga = e._geomed_args(kw)
-                w = C.cpu_geomed_weights(D, *ga) if C is not None else ref.geomed_weights(D, *ga).float()
-            elif rule == "cclip":
-                w = gar.cclip_weights_from_distances(C, D, n, f, *e._cclip_args(kw), m)
-            elif rule == "dnc":
-                w = gar.dnc_weights_from_distances(C, D, cfg.m if cfg.m is not None else n - f, e._dnc_iters(kw))
-            else:
-                w = C.cpu_brute_weights(D, f) if C is not None else ref.brute_weights(D, f).float()
+                    return C.cpu_coordwise(X, gar._MODE["bulyan-tail"], f, t - 2 * f, w.reshape(-1), t, 0, 1.0)
+                return gar._torch_closest_mean(w @ X, t - 2 * f)
             e.last_weights = w
             return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
         if rule == "average":

@@ -121,6 +121,27 @@ float* fptr(const at::Tensor& t) {
   return t.data_ptr<float>();
 }
 
+// What the bindings of the one-workgroup selections on the Gram (gar_select.hpp) check alike: 1 <= n <= kMaxRows,
+// batch >= 1, GPU tensors, gram [batch][np][np] and every buffer with at least `per` elements per problem.
+// Returns np = gram_padded(n).
+struct SelectBuf {
+  const at::Tensor& t;
+  int64_t per;
+};
+int check_select(const char* who, const at::Tensor& gram, int n, int batch, std::initializer_list<SelectBuf> bufs) {
+  TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, who, ": 1 <= n <= ", garfield::kMaxRows);
+  TORCH_CHECK(batch >= 1, who, ": batch must be >= 1");
+  const int np = garfield::gpu::gram_padded(n);
+  bool gpu = gram.is_cuda(), fits = gram.numel() >= static_cast<int64_t>(batch) * np * np;
+  for (const SelectBuf& b : bufs) {
+    gpu = gpu && b.t.is_cuda();
+    fits = fits && b.t.numel() >= batch * b.per;
+  }
+  TORCH_CHECK(gpu, who, ": GPU tensors expected");
+  TORCH_CHECK(fits, who, ": buffers too small for the batch");
+  return np;
+}
+
 // Arguments of gpu_ / cpu_worker_momentum: X [k, >= hi] rows of unit element stride (any row stride),
 // M [k, ld >= hi] contiguous fp32, 0 <= lo <= hi, 0 <= beta < 1. Returns X's dtype code.
 int check_worker_momentum(const at::Tensor& X, const at::Tensor& M, int64_t lo, int64_t hi, double beta, bool gpu) {
@@ -2018,13 +2039,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            "Split-K MFMA Gram matrix G·Gᵀ (fp32 [np, np])");
   m.def("gpu_krum_select", [](const at::Tensor& gram, int n, int f, int mm, const at::Tensor& w, const at::Tensor& order,
                               const at::Tensor& scores, int batch) {
-    c10::hip::HIPGuard guard(gram.device().index());
+    const int np = check_select("gpu_krum_select", gram, n, batch, {{w, n}, {order, n}, {scores, n}});
     TORCH_CHECK(order.scalar_type() == at::kInt, "order must be int32");
-    TORCH_CHECK(batch >= 1, "batch must be >= 1");
-    const int np = garfield::gpu::gram_padded(n);
-    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && w.numel() >= static_cast<int64_t>(batch) * n &&
-                    order.numel() >= static_cast<int64_t>(batch) * n && scores.numel() >= static_cast<int64_t>(batch) * n,
-                "gpu_krum_select: buffers too small for the batch");
+    c10::hip::HIPGuard guard(gram.device().index());
     garfield::gpu::krum_select(fptr(gram), np, n, f, mm, fptr(w), order.data_ptr<int>(), fptr(scores),
                                stream_of(gram.device()), batch);
   }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("m"), py::arg("weights"), py::arg("order"),
@@ -2032,15 +2049,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "Multi-Krum selection weights on device; batch > 1: gram [batch, np, np] -> weights [batch, n]");
   m.def("gpu_geomed_select", [](const at::Tensor& gram, int n, int iters, double nu, const at::Tensor& w,
                                 const at::Tensor& dists, int batch) {
-    c10::hip::HIPGuard guard(gram.device().index());
-    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_geomed_select: 1 <= n <= ", garfield::kMaxRows);
+    const int np = check_select("gpu_geomed_select", gram, n, batch, {{w, n}, {dists, n}});
     TORCH_CHECK(iters >= 1 && nu > 0.0, "gpu_geomed_select: iters >= 1 and nu > 0");
-    TORCH_CHECK(batch >= 1, "batch must be >= 1");
-    TORCH_CHECK(gram.is_cuda() && w.is_cuda() && dists.is_cuda(), "gpu_geomed_select: GPU tensors expected");
-    const int np = garfield::gpu::gram_padded(n);
-    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && w.numel() >= static_cast<int64_t>(batch) * n &&
-                    dists.numel() >= static_cast<int64_t>(batch) * n,
-                "gpu_geomed_select: buffers too small for the batch");
+    c10::hip::HIPGuard guard(gram.device().index());
     garfield::gpu::geomed_select(fptr(gram), np, n, iters, nu, fptr(w), fptr(dists), stream_of(gram.device()), batch);
   }, py::arg("gram"), py::arg("n"), py::arg("iters"), py::arg("nu"), py::arg("weights"), py::arg("dists"),
      py::arg("batch") = 1,
@@ -2048,17 +2059,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "distance to every row; batch > 1: gram [batch, np, np] -> weights / dists [batch, n]");
   m.def("gpu_cclip_select", [](const at::Tensor& gram, int n, int nw, const c10::optional<at::Tensor>& a0, double tau,
                                int f, int iters, const at::Tensor& w, const at::Tensor& dists, int batch) {
-    c10::hip::HIPGuard guard(gram.device().index());
-    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_cclip_select: 1 <= n <= ", garfield::kMaxRows);
+    const int np = check_select("gpu_cclip_select", gram, n, batch, {{w, n}, {dists, n}});
     TORCH_CHECK(nw >= 1 && nw <= n, "gpu_cclip_select: 1 <= nw <= n");
     TORCH_CHECK(iters >= 1 && f >= 0, "gpu_cclip_select: iters >= 1 and f >= 0");
     TORCH_CHECK(tau == tau, "gpu_cclip_select: tau must not be NaN");
-    TORCH_CHECK(batch >= 1, "batch must be >= 1");
-    TORCH_CHECK(gram.is_cuda() && w.is_cuda() && dists.is_cuda(), "gpu_cclip_select: GPU tensors expected");
-    const int np = garfield::gpu::gram_padded(n);
-    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && w.numel() >= static_cast<int64_t>(batch) * n &&
-                    dists.numel() >= static_cast<int64_t>(batch) * n,
-                "gpu_cclip_select: buffers too small for the batch");
+    c10::hip::HIPGuard guard(gram.device().index());
     const float* start = nullptr;
     if (a0.has_value()) {
       TORCH_CHECK(a0->is_cuda() && a0->scalar_type() == at::kFloat && a0->is_contiguous() &&
@@ -2075,15 +2080,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "data; dists = the centre's distance to every valid worker; batch > 1: gram [batch, np, np] -> weights / dists [batch, n]");
   m.def("gpu_dnc_select", [](const at::Tensor& gram, int n, int mm, int iters, const at::Tensor& w,
                              const at::Tensor& scores, int batch) {
-    c10::hip::HIPGuard guard(gram.device().index());
-    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_dnc_select: 1 <= n <= ", garfield::kMaxRows);
+    const int np = check_select("gpu_dnc_select", gram, n, batch, {{w, n}, {scores, n}});
     TORCH_CHECK(mm >= 1 && mm <= n && iters >= 1, "gpu_dnc_select: 1 <= m <= n and iters >= 1");
-    TORCH_CHECK(batch >= 1, "batch must be >= 1");
-    TORCH_CHECK(gram.is_cuda() && w.is_cuda() && scores.is_cuda(), "gpu_dnc_select: GPU tensors expected");
-    const int np = garfield::gpu::gram_padded(n);
-    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && w.numel() >= static_cast<int64_t>(batch) * n &&
-                    scores.numel() >= static_cast<int64_t>(batch) * n,
-                "gpu_dnc_select: buffers too small for the batch");
+    c10::hip::HIPGuard guard(gram.device().index());
     garfield::gpu::dnc_select(fptr(gram), np, n, mm, iters, fptr(w), fptr(scores), stream_of(gram.device()), batch);
   }, py::arg("gram"), py::arg("n"), py::arg("m"), py::arg("iters"), py::arg("weights"), py::arg("scores"),
      py::arg("batch") = 1,
@@ -2092,17 +2091,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "weights / scores [batch, n]");
   m.def("gpu_nnm_mix", [](const at::Tensor& gram, int n, int f, const at::Tensor& H, const at::Tensor& masks,
                           int batch) {
-    c10::hip::HIPGuard guard(gram.device().index());
-    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_nnm_mix: 1 <= n <= ", garfield::kMaxRows);
+    const int64_t hp = garfield::gpu::gram_padded(n);   // H has the Gram's shape
+    const int np = check_select("gpu_nnm_mix", gram, n, batch, {{H, hp * hp}, {masks, 2 * n}});
     TORCH_CHECK(f >= 0 && f < n, "gpu_nnm_mix: 0 <= f < n");
-    TORCH_CHECK(batch >= 1, "batch must be >= 1");
-    TORCH_CHECK(gram.is_cuda() && H.is_cuda() && masks.is_cuda(), "gpu_nnm_mix: GPU tensors expected");
     TORCH_CHECK(masks.scalar_type() == at::kLong && masks.is_contiguous(), "gpu_nnm_mix: masks must be contiguous int64");
-    const int np = garfield::gpu::gram_padded(n);
-    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && H.numel() >= static_cast<int64_t>(batch) * np * np &&
-                    masks.numel() >= static_cast<int64_t>(batch) * 2 * n,
-                "gpu_nnm_mix: buffers too small for the batch");
     TORCH_CHECK(fptr(gram) != fptr(H), "gpu_nnm_mix: H must not alias the Gram");
+    c10::hip::HIPGuard guard(gram.device().index());
     garfield::gpu::nnm_mix(fptr(gram), np, n, f, fptr(H), reinterpret_cast<unsigned long long*>(masks.data_ptr<int64_t>()),
                            stream_of(gram.device()), batch);
   }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("H"), py::arg("masks"), py::arg("batch") = 1,
@@ -2124,15 +2118,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("a"), py::arg("masks"), py::arg("n"), py::arg("f"), py::arg("w"), py::arg("batch") = 1,
      "Fold weights a [n] over the mixed rows back onto the original rows: w_j = sum of a_i over the sets holding j, / (n - f)");
   m.def("gpu_nnm_sets", [](const at::Tensor& gram, int n, int f, const at::Tensor& masks, int batch) {
-    c10::hip::HIPGuard guard(gram.device().index());
-    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_nnm_sets: 1 <= n <= ", garfield::kMaxRows);
+    const int np = check_select("gpu_nnm_sets", gram, n, batch, {{masks, 2 * n}});
     TORCH_CHECK(f >= 0 && f < n, "gpu_nnm_sets: 0 <= f < n");
-    TORCH_CHECK(batch >= 1, "batch must be >= 1");
-    TORCH_CHECK(gram.is_cuda() && masks.is_cuda(), "gpu_nnm_sets: GPU tensors expected");
     TORCH_CHECK(masks.scalar_type() == at::kLong && masks.is_contiguous(), "gpu_nnm_sets: masks must be contiguous int64");
-    const int np = garfield::gpu::gram_padded(n);
-    TORCH_CHECK(gram.numel() >= static_cast<int64_t>(batch) * np * np && masks.numel() >= static_cast<int64_t>(batch) * 2 * n,
-                "gpu_nnm_sets: buffers too small for the batch");
+    c10::hip::HIPGuard guard(gram.device().index());
     garfield::gpu::nnm_sets(fptr(gram), np, n, f, reinterpret_cast<unsigned long long*>(masks.data_ptr<int64_t>()),
                             stream_of(gram.device()), batch);
   }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("masks"), py::arg("batch") = 1,
@@ -2176,11 +2165,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            "(local coordinates), seg_off (global), base (global coordinate of local 0), weights, param, mom, "
            "shadow|None, lr, momentum, dampening, weight_decay, nesterov, first_step)");
   m.def("gpu_bulyan_select", [](const at::Tensor& gram, int n, int f, int mm, int t, const at::Tensor& W, int batch) {
+    const int np = check_select("gpu_bulyan_select", gram, n, batch, {{W, static_cast<int64_t>(t) * n}});
     c10::hip::HIPGuard guard(gram.device().index());
-    TORCH_CHECK(batch >= 1, "batch must be >= 1");
-    const int np = garfield::gpu::gram_padded(n);
-    TORCH_CHECK(W.numel() >= static_cast<int64_t>(batch) * t * n && gram.numel() >= static_cast<int64_t>(batch) * np * np,
-                "gpu_bulyan_select: buffers too small for the batch");
     garfield::gpu::bulyan_select(fptr(gram), np, n, f, mm, t, fptr(W), stream_of(gram.device()), batch);
   }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("m"), py::arg("t"), py::arg("W"), py::arg("batch") = 1,
      "Bulyan's t selection steps on device: W [t, n]; batch > 1: gram [batch, np, np] -> W [batch, t, n]");

@@ -15,7 +15,7 @@
 // each lane owning columns (lane, lane + 64). All sums are fp64 in the fixed butterfly order of
 // k_geomed_select, the trip count is fixed, the data-derived radius (the k-th smallest r) is found
 // by rank counting: same Gram in, same bits out, on every rank. No atomics.
-#include "gar_device.hpp"
+#include "gar_select.hpp"
 
 namespace garfield {
 namespace gpu {
@@ -41,24 +41,8 @@ __global__ __launch_bounds__(1024) void k_cclip_select(const float* __restrict__
   float* D = reinterpret_cast<float*>(lds64 + 4 * n + 1);   // n * (n + 1), diagonal 0
   int* valid = reinterpret_cast<int*>(D + n * (n + 1));      // n
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int pitch = n + 1;
 
-  fill_distances(gram, np, n, D, 0.f);
-  __syncthreads();
-  // a row is valid when it has a finite off-diagonal distance
-  for (int i = wave; i < n; i += 16) {
-    float cnt = 0.f;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int j = lane + 64 * c;
-      if (j < n && j != i && D[i * pitch + j] != kInf) cnt += 1.f;
-    }
-    cnt = wave_sum(cnt);
-    if (lane == 0) valid[i] = cnt > 0.f;
-  }
-  __syncthreads();
-  int nv = 0;   // |V|: the valid workers
-  for (int i = 0; i < nw; ++i) nv += valid[i];
+  const int nv = load_valid_distances(gram, np, n, nw, D, valid);   // |V|: the valid workers
   const int me = threadIdx.x;
   if (nv == 0) {   // one worker or every pair non-finite: plain average of the workers
     if (me < n) {
@@ -70,12 +54,7 @@ __global__ __launch_bounds__(1024) void k_cclip_select(const float* __restrict__
   const double nvd = static_cast<double>(nv);
   const bool worker = me < nw && valid[me];
   const double uniform = worker ? 1.0 / nvd : 0.0;
-  // an infinite distance between two valid rows (overflow) counts as 0; invalid rows carry a = 0
-  // and zeroed distances, so they add exact zeros to every sum
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    const int i = e / n, j = e % n;
-    if (D[i * pitch + j] == kInf) D[i * pitch + j] = 0.f;
-  }
+  zero_infinite_distances(D, n);   // invalid rows carry a = 0 and zeroed distances: exact zeros in every sum
   if (me < n) {
     A[me] = a0 ? (valid[me] ? static_cast<double>(a0[me]) : 0.0) : uniform;
     S[me] = 0.0;
@@ -92,17 +71,7 @@ __global__ __launch_bounds__(1024) void k_cclip_select(const float* __restrict__
   const int k = max(nv - f, 1);
   double r = 0.0;
   for (int it = 0; it < iters; ++it) {
-    for (int i = wave; i < n; i += 16) {
-      const float* row = D + i * pitch;
-      double acc = 0.0;
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int j = lane + 64 * c;
-        if (j < n) acc += A[j] * static_cast<double>(row[j]);
-      }
-      acc = wave_sum_f64(acc);
-      if (lane == 0) S[i] = acc;
-    }
+    dist_matvec(D, n, A, S);
     __syncthreads();
     const double q = 0.5 * wave_dot(A, S, n, lane);
     if (worker) {
@@ -143,22 +112,15 @@ __global__ __launch_bounds__(1024) void k_cclip_select(const float* __restrict__
   }
 }
 
+// 128 x 129 fp32 distances + 4 x 128 fp64 vectors = 70.6 KB at n = 128
 static size_t cclip_lds_bytes(int n) {
   return static_cast<size_t>(4 * n + 1) * sizeof(double) + static_cast<size_t>(n * (n + 1) + n) * sizeof(float);
 }
 
 void cclip_select(const float* gram_in, int np, int n, int nw, const float* a0, double tau, int f, int iters,
                   float* weights, float* dists, hipStream_t stream, int batch) {
-  // 128 x 129 fp32 distances + 4 x 128 fp64 vectors = 70.6 KB > the 64 KB default: opt in to 96 KB
-  static bool once = [] {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cclip_select),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-      (void)hipGetLastError();  // never leave a sticky error for the framework to trip over
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL(k_cclip_select, dim3(batch), dim3(1024), cclip_lds_bytes(n), stream, gram_in, np, n, nw, a0, tau,
-                     f, iters, weights, dists);
+  launch_select<k_cclip_select>(batch, cclip_lds_bytes(n), stream, gram_in, np, n, nw, a0, tau, f, iters, weights,
+                                dists);
 }
 
 }  // namespace gpu

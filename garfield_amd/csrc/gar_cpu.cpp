@@ -103,36 +103,60 @@ std::vector<float> krum_weights(const std::vector<double>& D, size_t n, size_t f
   return w;
 }
 
+// The validity policy of the iterated selections (docs/GAR_SEMANTICS.md "Geometric median"; on the GPU:
+// gar_select.hpp). valid[i]: row i has a finite off-diagonal distance; nv = |V|, counted over the rows [0, nw).
+struct ValidRows {
+  std::vector<char> valid;
+  size_t nv = 0;
+};
+static ValidRows valid_rows(const std::vector<double>& D, size_t n, size_t nw) {
+  ValidRows v{std::vector<char>(n, 0), 0};
+  for (size_t i = 0; i < n; ++i) {
+    for (size_t j = 0; j < n; ++j)
+      if (j != i && std::isfinite(D[i * n + j])) v.valid[i] = 1;
+    if (i < nw) v.nv += v.valid[i];
+  }
+  return v;
+}
+
+// The usable distance: the diagonal and an infinite distance between two valid rows count as 0.
+struct Usable {
+  const std::vector<double>& D;
+  size_t n;
+  double operator()(size_t i, size_t j) const {
+    const double v = D[i * n + j];
+    return (i != j && std::isfinite(v)) ? v : 0.0;
+  }
+};
+
+// s = D a over the valid rows, in index order; returns q = ½ aᵀ s (geometric median, centered clipping).
+static double dist_quadratic(const Usable& dist, const std::vector<char>& valid, const std::vector<double>& a,
+                             std::vector<double>& s) {
+  const size_t n = a.size();
+  for (size_t i = 0; i < n; ++i) {
+    if (!valid[i]) continue;
+    double acc = 0.0;
+    for (size_t j = 0; j < n; ++j)
+      if (valid[j]) acc += a[j] * dist(i, j);
+    s[i] = acc;
+  }
+  double q = 0.0;
+  for (size_t i = 0; i < n; ++i)
+    if (valid[i]) q += a[i] * s[i];
+  return 0.5 * q;
+}
+
 // Smoothed Weiszfeld on the distance matrix alone (docs/GAR_SEMANTICS.md "Geometric median"):
 // exactly `iters` rounds, every sum in index order over the valid rows.
 std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t iters, double nu) {
-  std::vector<char> valid(n, 0);
-  size_t nv = 0;
-  for (size_t i = 0; i < n; ++i) {
-    for (size_t j = 0; j < n; ++j)
-      if (j != i && std::isfinite(D[i * n + j])) valid[i] = 1;
-    nv += valid[i];
-  }
+  const auto [valid, nv] = valid_rows(D, n, n);
   if (nv == 0) return std::vector<float>(n, 1.f / static_cast<float>(n));
-  auto dist = [&](size_t i, size_t j) {
-    const double v = D[i * n + j];
-    return (i != j && std::isfinite(v)) ? v : 0.0;
-  };
+  const Usable dist{D, n};
   std::vector<double> a(n, 0.0), s(n, 0.0), b(n, 0.0);
   for (size_t i = 0; i < n; ++i)
     if (valid[i]) a[i] = 1.0 / static_cast<double>(nv);
   for (size_t it = 0; it < iters; ++it) {
-    for (size_t i = 0; i < n; ++i) {
-      if (!valid[i]) continue;
-      double acc = 0.0;
-      for (size_t j = 0; j < n; ++j)
-        if (valid[j]) acc += a[j] * dist(i, j);
-      s[i] = acc;
-    }
-    double q = 0.0;
-    for (size_t i = 0; i < n; ++i)
-      if (valid[i]) q += a[i] * s[i];
-    q *= 0.5;
+    const double q = dist_quadratic(dist, valid, a, s);
     double tot = 0.0;
     for (size_t i = 0; i < n; ++i) {
       if (!valid[i]) continue;
@@ -152,21 +176,12 @@ std::vector<float> geomed_weights(const std::vector<double>& D, size_t n, size_t
 // valid rows; the min(m, |V|) lowest fp32 scores are kept.
 std::vector<float> dnc_weights(const std::vector<double>& D, size_t n, size_t m, size_t iters,
                                std::vector<float>* scores_out) {
-  std::vector<char> valid(n, 0);
-  size_t nv = 0;
-  for (size_t i = 0; i < n; ++i) {
-    for (size_t j = 0; j < n; ++j)
-      if (j != i && std::isfinite(D[i * n + j])) valid[i] = 1;
-    nv += valid[i];
-  }
+  const auto [valid, nv] = valid_rows(D, n, n);
   if (nv == 0) {
     if (scores_out) scores_out->assign(n, 0.f);
     return std::vector<float>(n, static_cast<float>(1.0 / static_cast<double>(n)));
   }
-  auto dist = [&](size_t i, size_t j) {
-    const double v = D[i * n + j];
-    return (i != j && std::isfinite(v)) ? v : 0.0;
-  };
+  const Usable dist{D, n};
   const double nvd = static_cast<double>(nv);
   const size_t kv = std::min(m, nv);
   std::vector<double> r(n, 0.0), b(n, 0.0), u(n, 0.0), t(n, 0.0);
@@ -231,22 +246,13 @@ std::vector<float> dnc_weights(const std::vector<double>& D, size_t n, size_t m,
 // exactly `iters` rounds, every sum in index order.
 std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t nw, const std::vector<double>& a0,
                                  double tau, size_t f, size_t iters) {
-  std::vector<char> valid(n, 0);
-  size_t nv = 0;   // |V|: the valid workers
-  for (size_t i = 0; i < n; ++i) {
-    for (size_t j = 0; j < n; ++j)
-      if (j != i && std::isfinite(D[i * n + j])) valid[i] = 1;
-    if (i < nw) nv += valid[i];
-  }
+  const auto [valid, nv] = valid_rows(D, n, nw);   // |V|: the valid workers
   std::vector<float> w(n, 0.f);
   if (nv == 0) {
     for (size_t i = 0; i < nw; ++i) w[i] = static_cast<float>(1.0 / static_cast<double>(nw));
     return w;
   }
-  auto dist = [&](size_t i, size_t j) {
-    const double v = D[i * n + j];
-    return (i != j && std::isfinite(v)) ? v : 0.0;
-  };
+  const Usable dist{D, n};
   const double nvd = static_cast<double>(nv);
   std::vector<double> a(n, 0.0), s(n, 0.0), r(n, 0.0), lam(n, 0.0);
   double tot = 0.0;
@@ -260,17 +266,7 @@ std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t 
   }
   const size_t k = nv > f ? nv - f : 1;
   for (size_t it = 0; it < iters; ++it) {
-    for (size_t i = 0; i < n; ++i) {
-      if (!valid[i]) continue;
-      double acc = 0.0;
-      for (size_t j = 0; j < n; ++j)
-        if (valid[j]) acc += a[j] * dist(i, j);
-      s[i] = acc;
-    }
-    double q = 0.0;
-    for (size_t i = 0; i < n; ++i)
-      if (valid[i]) q += a[i] * s[i];
-    q *= 0.5;
+    const double q = dist_quadratic(dist, valid, a, s);
     for (size_t i = 0; i < nw; ++i)
       if (valid[i]) r[i] = std::sqrt(std::max(s[i] - q, 0.0));
     double t = tau;

@@ -1,5 +1,6 @@
 // Device-side helpers shared by the gfx950 aggregation kernels (dtype
-// conversion, vector loads/stores, wave reductions, register sorting networks).
+// conversion, vector loads/stores, wave reductions, register sorting networks). What only the
+// one-workgroup selections on the Gram use is in gar_select.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -220,71 +221,8 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   return v;
 }
 
-// Σ_{i < n} x[i] y[i] (y == nullptr: Σ x[i]) by one wave, n <= 128; identical on every wave
-__device__ __forceinline__ double wave_dot(const double* x, const double* y, int n, int lane) {
-  double acc = 0.0;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int i = lane + 64 * c;
-    if (i < n) acc += y ? x[i] * y[i] : x[i];
-  }
-  return wave_sum_f64(acc);
-}
-
-// Squared distances D (LDS, pitch n + 1) from a Gram matrix (pitch np) by the whole workgroup:
-// non-finite -> +inf, clamped at 0, `diag` on the diagonal. Shared by the one-workgroup selections.
-__device__ __forceinline__ void fill_distances(const float* __restrict__ gram, int np, int n, float* D,
-                                               float diag = kInf) {
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    const int i = e / n, j = e % n;
-    float v;
-    if (i == j) {
-      v = diag;
-    } else {
-      v = gram[i * np + i] + gram[j * np + j] - 2.f * gram[i * np + j];
-      if (!isfinite(v)) v = kInf;
-      v = fmaxf(v, 0.f);
-    }
-    D[i * (n + 1) + j] = v;
-  }
-}
-
-// The neighbour sets of nearest-neighbour mixing from the distances D of fill_distances (diagonal 0) by
-// the whole workgroup: S_i = row i, then the c - 1 nearest others by (distance, index), as ranks
-// counted by one lane per column and a ballot. Row i is wave i % (waves)'s; a set is two 64-bit mask
-// words, written to `masks` and (when given) to the LDS copy Mk. Shared by k_nnm_mix and k_nnm_sets.
-__device__ __forceinline__ void nnm_build_sets(const float* D, int n, int c, unsigned long long* Mk,
-                                               unsigned long long* __restrict__ masks) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
-  const int pitch = n + 1;
-  for (int i = wave; i < n; i += nwaves) {
-    const float* row = D + i * pitch;
-#pragma unroll
-    for (int cc = 0; cc < 2; ++cc) {
-      const int j = lane + 64 * cc;
-      bool member = false;
-      if (j < n) {
-        if (j == i) {
-          member = true;
-        } else {
-          const float dj = row[j];
-          int rank = 0;
-          for (int k = 0; k < n; ++k) {
-            const float dk = row[k];
-            rank += (k != i) && (dk < dj || (dk == dj && k < j));
-          }
-          member = rank < c - 1;
-        }
-      }
-      const unsigned long long b = __ballot(member);
-      if (lane == 0) {
-        if (Mk) Mk[2 * i + cc] = b;
-        masks[2 * i + cc] = b;
-      }
-    }
-  }
-}
-
+// rank of s[i] among s[0..n) by (value, index), NaN as +inf (the one-workgroup selections' other shared
+// helpers are in gar_select.hpp; k_aksel_select in gar_combine.hip ranks with this one too)
 __device__ __forceinline__ int score_rank(const float* s, int n, int i) {
   const float si = sanitize_inf(s[i]);
   int rank = 0;

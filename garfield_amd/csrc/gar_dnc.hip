@@ -15,7 +15,7 @@
 // of t in registers (three fp64 wave sums): t is double-buffered, so a round costs one barrier.
 // All sums are fp64 in a fixed pairing of the lanes and the trip count is fixed: same Gram in, same
 // bits out, on every rank. No atomics.
-#include "gar_device.hpp"
+#include "gar_select.hpp"
 
 namespace garfield {
 namespace gpu {
@@ -60,22 +60,7 @@ __global__ __launch_bounds__(1024) void k_dnc_select(const float* __restrict__ g
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int pitch = n + 1;
 
-  fill_distances(gram, np, n, D, 0.f);   // the selections' distances, with a zero diagonal
-  __syncthreads();
-  // a row is valid when it has a finite off-diagonal distance
-  for (int i = wave; i < n; i += 16) {
-    float cnt = 0.f;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      const int j = lane + 64 * c;
-      if (j < n && j != i && D[i * pitch + j] != kInf) cnt += 1.f;
-    }
-    cnt = wave_sum(cnt);
-    if (lane == 0) valid[i] = cnt > 0.f;
-  }
-  __syncthreads();
-  int nv = 0;
-  for (int i = 0; i < n; ++i) nv += valid[i];
+  const int nv = load_valid_distances(gram, np, n, n, D, valid);   // docs/GAR_SEMANTICS.md: the validity policy
   const int me = threadIdx.x;
   if (nv == 0) {   // n == 1 or every pair non-finite: plain average (uniform branch)
     if (me < n) {
@@ -86,12 +71,7 @@ __global__ __launch_bounds__(1024) void k_dnc_select(const float* __restrict__ g
   }
   const double nvd = static_cast<double>(nv);
   const int kv = min(m, nv);   // non-finite rows use up the removal budget first
-  // an infinite distance between two valid rows (overflow) counts as 0; an invalid row's distances
-  // are all zeroed, so it adds exact zeros to every sum
-  for (int e = threadIdx.x; e < n * n; e += blockDim.x) {
-    const int i = e / n, j = e % n;
-    if (D[i * pitch + j] == kInf) D[i * pitch + j] = 0.f;
-  }
+  zero_infinite_distances(D, n);   // an invalid row's distances are all zeroed: exact zeros in every sum
   __syncthreads();
   for (int i = wave; i < n; i += 16) {
     const float* row = D + i * pitch;
@@ -165,22 +145,14 @@ __global__ __launch_bounds__(1024) void k_dnc_select(const float* __restrict__ g
   }
 }
 
+// 128 x 129 fp32 distances + 3 x 128 fp64 vectors + scores and flags = 69.1 KB at n = 128
 static size_t dnc_lds_bytes(int n) {
   return static_cast<size_t>(3 * n) * sizeof(double) + static_cast<size_t>(n * (n + 1) + 2 * n) * sizeof(float);
 }
 
 void dnc_select(const float* gram_in, int np, int n, int m, int iters, float* weights, float* scores,
                 hipStream_t stream, int batch) {
-  // 128 x 129 fp32 distances + 3 x 128 fp64 vectors = 69.1 KB > the 64 KB default: opt in to 96 KB
-  static bool once = [] {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dnc_select),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-      (void)hipGetLastError();  // never leave a sticky error for the framework to trip over
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL(k_dnc_select, dim3(batch), dim3(1024), dnc_lds_bytes(n), stream, gram_in, np, n, m, iters,
-                     weights, scores);
+  launch_select<k_dnc_select>(batch, dnc_lds_bytes(n), stream, gram_in, np, n, m, iters, weights, scores);
 }
 
 }  // namespace gpu

@@ -23,6 +23,8 @@ void gram(const RowTable& rows, int n, int64_t d, int dt, float* slabs, int grid
           float* gram, hipStream_t stream);
 
 // ---- Selection (one workgroup, on device, no host round-trip) --------------
+// krum, bulyan, geomed, cclip, dnc, nnm_mix and nnm_sets share gar_select.hpp: the distances from the Gram, the
+// validity policy, and launch_select (1024 threads per problem, n <= kMaxRows).
 // weights[n] (fp32), order[n] (gradient ids by increasing score), scores[n]
 // batch > 1: `batch` independent problems, gram [batch][np][np] -> weights/order/scores [batch][n]
 void krum_select(const float* gram, int np, int n, int f, int m, float* weights,

@@ -21,7 +21,7 @@
 //             intermediate).
 #include <cstdlib>
 
-#include "gar_device.hpp"
+#include "gar_select.hpp"
 
 namespace garfield {
 namespace gpu {
@@ -195,29 +195,8 @@ __global__ __launch_bounds__(256) void k_gram_reduce(const float* __restrict__ s
 // (D_ik, k) < (D_ij, j)}, which gives a strict total order, hence the same
 // selection on every rank of a data-parallel job and on the CPU oracle.
 
-// D (pitch n+1) from the Gram: fill_distances (gar_device.hpp), +inf on the diagonal.
-
-// Krum score of row i (sum of the q smallest off-diagonal distances); when
-// keep != nullptr, also reports whether column j is among the q nearest.
-__device__ float row_score(const float* D, int n, int i, int q, int lane, bool keep[2]) {
-  const float* row = D + i * (n + 1);
-  float contrib = 0.f;
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int j = lane + 64 * c;
-    keep[c] = false;
-    if (j < n && j != i) {
-      const float dj = row[j];
-      int rank = 0;
-      for (int k = 0; k < n; ++k) {
-        const float dk = row[k];
-        rank += (k != i) && (dk < dj || (dk == dj && k < j));
-      }
-      if (rank < q) { contrib += dj; keep[c] = true; }
-    }
-  }
-  return wave_sum(contrib);
-}
+// D (pitch n+1) from the Gram: fill_distances, +inf on the diagonal; the Krum score of a row: row_score
+// (both in gar_select.hpp).
 
 __global__ __launch_bounds__(1024) void k_krum_select(const float* __restrict__ gram, int np, int n,
                                                       int f, int m, float* __restrict__ weights,
@@ -469,28 +448,16 @@ void gram(const RowTable& rows, int n, int64_t d, int dt, float* slabs, int grid
 // ---------------------------------------------------------------------------
 // Selection
 
+// 128 x 129 fp32 distance matrix + scores = 66.6 KB at n = 128
 static size_t select_lds_bytes(int n) { return static_cast<size_t>(n * (n + 1) + n) * sizeof(float); }
-
-static void allow_big_lds(const void* fn) {
-  // 128 x 129 fp32 distance matrix + scores = 66.6 KB > the 64 KB default
-  // (n <= 128). Ask for 96 KB: the static __shared__ of the kernel counts against the 160 KB too.
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-    (void)hipGetLastError();  // never leave a sticky error for the framework to trip over
-}
 
 void krum_select(const float* gram_in, int np, int n, int f, int m, float* weights, int* order, float* scores,
                  hipStream_t stream, int batch) {
-  static bool once = (allow_big_lds(reinterpret_cast<const void*>(&k_krum_select)), true);
-  (void)once;
-  hipLaunchKernelGGL(k_krum_select, dim3(batch), dim3(1024), select_lds_bytes(n), stream, gram_in, np, n, f, m,
-                     weights, order, scores);
+  launch_select<k_krum_select>(batch, select_lds_bytes(n), stream, gram_in, np, n, f, m, weights, order, scores);
 }
 
 void bulyan_select(const float* gram_in, int np, int n, int f, int m, int t, float* W, hipStream_t stream, int batch) {
-  static bool once = (allow_big_lds(reinterpret_cast<const void*>(&k_bulyan_select)), true);
-  (void)once;
-  hipLaunchKernelGGL(k_bulyan_select, dim3(batch), dim3(1024), select_lds_bytes(n), stream, gram_in, np, n, f, m, t,
-                     W);
+  launch_select<k_bulyan_select>(batch, select_lds_bytes(n), stream, gram_in, np, n, f, m, t, W);
 }
 
 static unsigned long long host_binom(int a, int b) {

@@ -15,7 +15,7 @@
 // row: a later set builder can reuse everything after the ballot). All sums are fp64 over the set
 // members in ascending index, the inner sum over l first: equal sets give bit-equal M, hence an
 // exact zero distance, and the same Gram gives the same bits on every rank.
-#include "gar_device.hpp"
+#include "gar_select.hpp"
 
 namespace garfield {
 namespace gpu {
@@ -126,21 +126,14 @@ __global__ __launch_bounds__(128) void k_nnm_unmix(const float* __restrict__ a, 
   w[j] = tot == 0.0 ? 0.f : static_cast<float>(acc / tot / static_cast<double>(c));
 }
 
+// 128 x 129 fp32 distances + 128 x 16 fp64 R + sets and M_ii = 83.5 KB at n = 128
 static size_t nnm_lds_bytes(int n) {
   return static_cast<size_t>(n * kJB + 3 * n) * sizeof(double) + static_cast<size_t>(n * (n + 1)) * sizeof(float);
 }
 
 void nnm_mix(const float* gram_in, int np, int n, int f, float* H, unsigned long long* masks, hipStream_t stream,
              int batch) {
-  // 128 x 129 fp32 distances + 128 x 16 fp64 R + sets and M_ii = 83.5 KB > the 64 KB default: opt in to 96 KB
-  static bool once = [] {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nnm_mix), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            96 * 1024) != hipSuccess)
-      (void)hipGetLastError();  // never leave a sticky error for the framework to trip over
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL(k_nnm_mix, dim3(batch), dim3(1024), nnm_lds_bytes(n), stream, gram_in, np, n, n - f, H, masks);
+  launch_select<k_nnm_mix>(batch, nnm_lds_bytes(n), stream, gram_in, np, n, n - f, H, masks);
 }
 
 void nnm_unmix(const float* a, const unsigned long long* masks, int n, int f, float* w, hipStream_t stream,

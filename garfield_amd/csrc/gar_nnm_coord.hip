@@ -13,6 +13,7 @@
 //               k_bulyan_tail does, in plain IEEE sums (a non-finite member reaches exactly the sets
 //               that hold it).
 #include "gar_nnm_coord.hpp"
+#include "gar_select.hpp"
 
 namespace garfield {
 namespace gpu {
@@ -29,17 +30,11 @@ __global__ __launch_bounds__(1024) void k_nnm_sets(const float* __restrict__ gra
   nnm_build_sets(lds_d, n, c, nullptr, masks);
 }
 
+// 128 x 129 fp32 distances = 64.5 KB at n = 128
+static size_t nnm_sets_lds_bytes(int n) { return static_cast<size_t>(n) * (n + 1) * sizeof(float); }
+
 void nnm_sets(const float* gram_in, int np, int n, int f, unsigned long long* masks, hipStream_t stream, int batch) {
-  // 128 x 129 fp32 distances = 64.5 KB > the 64 KB default: opt in to 72 KB
-  static bool once = [] {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nnm_sets), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            72 * 1024) != hipSuccess)
-      (void)hipGetLastError();  // never leave a sticky error for the framework to trip over
-    return true;
-  }();
-  (void)once;
-  hipLaunchKernelGGL(k_nnm_sets, dim3(batch), dim3(1024), static_cast<size_t>(n) * (n + 1) * sizeof(float), stream,
-                     gram_in, np, n, n - f, masks);
+  launch_select<k_nnm_sets>(batch, nnm_sets_lds_bytes(n), stream, gram_in, np, n, n - f, masks);
 }
 
 namespace coord {

@@ -2311,6 +2311,65 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("rows"), py::arg("peers"), py::arg("empire"), py::arg("param"),
      "Colluding attacks in place on exchanged rows: rows[:peers] are the estimates, rows[peers:] the Byzantine rows "
      "(their honest gradient in, mean + z * std (lie) or -eps * mean (empire) of {own row} + estimates out)");
+  // Min-Max / Min-Sum colluding attacks (gar_agr_attack.hip); rows need not be 16-byte aligned
+  m.def("agr_grid", &garfield::gpu::agr_grid, py::arg("count"),
+        "Workgroups (rows of the partials buffer) of gpu_agr_stats over `count` coordinates");
+  m.def("gpu_agr_stats", [](const std::vector<at::Tensor>& rows, int pert, int64_t lo, int64_t hi,
+                            const at::Tensor& partials) {
+    RowSet rs = rows_from_list(rows, false);
+    TORCH_CHECK(rs.device.is_cuda() && rs.dt != garfield::kF64, "gpu_agr_stats: fp32, bf16 or fp16 GPU rows");
+    TORCH_CHECK(pert >= 0 && pert <= 2, "gpu_agr_stats: perturbation 0 (std), 1 (uv) or 2 (sgn)");
+    TORCH_CHECK(0 <= lo && lo <= hi && hi <= rs.d, "gpu_agr_stats: 0 <= lo <= hi <= row length");
+    const int grid = garfield::gpu::agr_grid(hi - lo);
+    TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kDouble && partials.is_contiguous() &&
+                    partials.numel() >= static_cast<int64_t>(grid) * (rs.n + 1),
+                "gpu_agr_stats: partials must be a contiguous fp64 GPU tensor of [agr_grid(hi - lo), k + 1]");
+    c10::hip::HIPGuard guard(rs.device.index());
+    garfield::gpu::agr_stats(rs.table, rs.n, lo, hi, rs.dt, pert, partials.data_ptr<double>(), stream_of(rs.device));
+    return grid;
+  }, py::arg("rows"), py::arg("perturbation"), py::arg("lo"), py::arg("hi"), py::arg("partials"),
+     "Statistics pass of the Min-Max / Min-Sum attacks over the coordinates [lo, hi) of the k estimate rows: "
+     "partials[g] = workgroup g's share of (b_0..b_{k-1}, c); returns the number of workgroups");
+  m.def("gpu_agr_reduce", [](const at::Tensor& parts, int nparts, int k, const at::Tensor& out) {
+    TORCH_CHECK(k >= 1 && k <= garfield::kMaxRows && nparts >= 1, "gpu_agr_reduce: 1 <= k <= ", garfield::kMaxRows,
+                " and nparts >= 1");
+    TORCH_CHECK(parts.is_cuda() && out.is_cuda() && parts.scalar_type() == at::kDouble && out.scalar_type() == at::kDouble &&
+                    parts.is_contiguous() && out.is_contiguous() &&
+                    parts.numel() >= static_cast<int64_t>(nparts) * (k + 1) && out.numel() >= k + 1,
+                "gpu_agr_reduce: contiguous fp64 GPU tensors parts [nparts, k + 1] and out [k + 1]");
+    c10::hip::HIPGuard guard(parts.device().index());
+    garfield::gpu::agr_reduce(parts.data_ptr<double>(), nparts, k, out.data_ptr<double>(), stream_of(parts.device()));
+  }, py::arg("parts"), py::arg("nparts"), py::arg("k"), py::arg("out"),
+     "out[k + 1] = the sum of nparts partial vectors in a fixed order (fp64)");
+  m.def("gpu_agr_solve", [](const at::Tensor& gram, int k, const at::Tensor& parts, int nparts, bool minsum,
+                            const at::Tensor& gamma, const at::Tensor& info) {
+    const int np = check_select("gpu_agr_solve", gram, k, 1, {{gamma, 1}});
+    TORCH_CHECK(nparts >= 1, "gpu_agr_solve: nparts >= 1");
+    TORCH_CHECK(parts.is_cuda() && info.is_cuda() && parts.scalar_type() == at::kDouble && info.scalar_type() == at::kDouble &&
+                    parts.is_contiguous() && info.is_contiguous() &&
+                    parts.numel() >= static_cast<int64_t>(nparts) * (k + 1) && info.numel() >= 2 + 2 * k,
+                "gpu_agr_solve: contiguous fp64 GPU tensors parts [nparts, k + 1] and info [2 + 2k]");
+    c10::hip::HIPGuard guard(gram.device().index());
+    garfield::gpu::agr_solve(fptr(gram), np, k, parts.data_ptr<double>(), nparts, minsum, fptr(gamma),
+                             info.data_ptr<double>(), stream_of(gram.device()));
+  }, py::arg("gram"), py::arg("k"), py::arg("parts"), py::arg("nparts"), py::arg("minsum"), py::arg("gamma"),
+     py::arg("info"),
+     "The closed-form γ of the Min-Max (minsum = False) or Min-Sum attack from the Gram of the k estimate rows and "
+     "the summed statistics: gamma[0] fp32; info = γ, R or S, a_i, b_i in fp64");
+  m.def("gpu_agr_write", [](const std::vector<at::Tensor>& rows, int64_t peers, const at::Tensor& gamma, int pert,
+                            int64_t lo, int64_t hi) {
+    RowSet rs = rows_from_list(rows, false);
+    TORCH_CHECK(rs.device.is_cuda() && rs.dt != garfield::kF64, "gpu_agr_write: fp32, bf16 or fp16 GPU rows");
+    TORCH_CHECK(peers >= 0 && peers <= rs.n, "gpu_agr_write: 0 <= peers <= number of rows");
+    TORCH_CHECK(pert >= 0 && pert <= 2, "gpu_agr_write: perturbation 0 (std), 1 (uv) or 2 (sgn)");
+    TORCH_CHECK(0 <= lo && lo <= hi && hi <= rs.d, "gpu_agr_write: 0 <= lo <= hi <= row length");
+    TORCH_CHECK(gamma.is_cuda() && gamma.numel() >= 1, "gpu_agr_write: gamma must be a GPU tensor");
+    c10::hip::HIPGuard guard(rs.device.index());
+    garfield::gpu::agr_write(rs.table, rs.n, static_cast<int>(peers), lo, hi, rs.dt, pert, fptr(gamma),
+                             stream_of(rs.device));
+  }, py::arg("rows"), py::arg("peers"), py::arg("gamma"), py::arg("perturbation"), py::arg("lo"), py::arg("hi"),
+     "Write pass of the Min-Max / Min-Sum attacks: rows[peers:] <- mean + gamma * perturbation of all the rows, "
+     "on the coordinates [lo, hi), in place");
   m.def("gpu_worker_momentum", [](const at::Tensor& X, const at::Tensor& M, int64_t lo, int64_t hi, double beta,
                                   bool first) {
     const int dt = check_worker_momentum(X, M, lo, hi, beta, true);

@@ -150,6 +150,26 @@ void collude(const RowTable& rows, int P, int T, int64_t d, int dt, bool empire,
 void aksel_select(const float* slabs, int grid, int n, int c, float* weights, float* dists,
                   hipStream_t stream);
 
+// ---- Adaptive colluding attacks Min-Max / Min-Sum (gar_agr_attack.hip) ----------------------------
+// The k <= kMaxRows rows are the colluders' estimates E: rows 0..P-1 the peers, rows P..k-1 the Byzantine
+// rows (holding their honest gradient). dt f32 / bf16 / f16; rows need no alignment (16-byte loads when
+// every row is 16-byte aligned at lo, single elements otherwise). Perturbation p per coordinate:
+enum AgrPerturbation : int { kAgrStd = 0, kAgrUv = 1, kAgrSgn = 2 };   // -σ (unbiased), -μ, -sign μ
+int agr_grid(int64_t count);   // workgroups of the streaming passes over `count` coordinates (<= 4096)
+// agr_stats: partials [agr_grid(hi - lo)][k + 1] fp64, each workgroup's share of b_i = Σ_x p (μ - e_i) and
+// c = Σ_x p² over the coordinates [lo, hi). agr_reduce: out[k + 1] = Σ of nparts such vectors, fixed order.
+void agr_stats(const RowTable& rows, int k, int64_t lo, int64_t hi, int dt, int pert, double* partials,
+               hipStream_t stream);
+void agr_reduce(const double* parts, int nparts, int k, double* out, hipStream_t stream);
+// agr_solve: one workgroup. parts [nparts][k + 1] summed in the same fixed order, the distances of the Gram
+// [np][np] of E -> gamma[0] (fp32) and info [2 + 2k] fp64 = γ, R (Min-Max) or S (Min-Sum), a_i, b_i.
+void agr_solve(const float* gram, int np, int k, const double* parts, int nparts, bool minsum, float* gamma,
+               double* info, hipStream_t stream);
+// agr_write: rows P..k-1 <- cast(fmaf(γ, p, μ)) on [lo, hi), γ read from device memory; nothing outside
+// [lo, hi) and no row below P is written.
+void agr_write(const RowTable& rows, int k, int P, int64_t lo, int64_t hi, int dt, int pert, const float* gamma,
+               hipStream_t stream);
+
 // ---- Worker-side momentum (worker_mom.hip), in place on coordinates [lo, hi) of k exchange rows ----
 // X: row r at X + r * xstride elements of dtype dt (f32 / bf16 / f16); M: the fp32 state, row r at
 // M + r * ld. First step: m <- g; later: m <- fmaf(beta, m, omega * g); then row <- cast(m). A

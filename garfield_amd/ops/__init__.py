@@ -5,3 +5,4 @@ from garfield_amd.ops.gar import (  # noqa: F401
     brute_weights, bulyan, bulyan_weights, combine, condense, gram, krum, krum_weights, median,
     pairwise_distances, prepare, trimmed_mean,
 )
+from garfield_amd.ops import agr_attack  # noqa: F401,E402  (imports ops.gar)

@@ -558,6 +558,52 @@ def worker_momentum(X, M, beta: float, first: bool, lo: int = 0, hi: int | None 
     return torch.where(finite, new, m), finite
 
 
+def agr_perturbation(X: torch.Tensor, perturbation: str) -> tuple:
+    """(μ, p) of the estimate rows ``X`` [k, d] (fp64): p = -σ (unbiased, 0 for k = 1), -μ or -sign μ."""
+    mu = X.mean(0)
+    if perturbation == "std":
+        p = -X.std(0, unbiased=True) if X.shape[0] > 1 else torch.zeros_like(mu)
+    elif perturbation == "uv":
+        p = -mu
+    elif perturbation == "sgn":
+        p = -torch.sign(mu)
+    else:
+        raise ValueError(f"unknown perturbation {perturbation!r}; available: 'std', 'uv', 'sgn'")
+    return mu, p
+
+
+def agr_attack(E, objective: str, perturbation: str = "std") -> tuple:
+    """The Min-Max / Min-Sum colluding attacks (docs/GAR_SEMANTICS.md "Adaptive colluding attacks") on the
+    estimate rows ``E`` [k, d], on the vectors: ``(m, γ)`` with m = μ + γ p and γ the largest value with
+    max_i ‖m - e_i‖² <= R = max_ij ‖e_i - e_j‖² (``objective`` "minmax") or Σ_i ‖m - e_i‖² <= S =
+    max_i Σ_j ‖e_i - e_j‖² ("minsum"), in closed form from ‖m - e_i‖² = a_i + 2 γ b_i + γ² c. γ = 0 for
+    k = 1, c = 0 or any non-finite quantity. Returns (fp64 [d], float)."""
+    if objective not in ("minmax", "minsum"):
+        raise ValueError(f"unknown objective {objective!r}; available: 'minmax', 'minsum'")
+    X = _g(E)
+    k = X.shape[0]
+    mu, p = agr_perturbation(X, perturbation)
+    D = torch.zeros((k, k), dtype=torch.float64)
+    for i in range(k):
+        D[i] = ((X - X[i]) ** 2).sum(1)
+    a = ((mu - X) ** 2).sum(1)
+    b = (p * (mu - X)).sum(1)
+    c = float((p * p).sum())
+    bound = float(D.max()) if objective == "minmax" else float(D.sum(1).max())
+    gamma = 0.0
+    if k > 1 and c > 0 and math.isfinite(c) and math.isfinite(bound) and bool(torch.isfinite(a).all()) \
+            and bool(torch.isfinite(b).all()):
+        if objective == "minmax":
+            gamma = float(((-b + torch.sqrt(b * b + c * (bound - a).clamp(min=0))) / c).min())
+        else:
+            gamma = math.sqrt(max(bound - float(a.sum()), 0.0) / (k * c))
+        if not math.isfinite(gamma):
+            gamma = 0.0
+    if gamma == 0.0:
+        return mu.clone(), 0.0      # also keeps a non-finite p out of m
+    return mu + gamma * p, gamma
+
+
 def aksel(G, f: int, mode: str = "mid") -> torch.Tensor:
     X = _g(G)
     n = X.shape[0]

@@ -35,9 +35,9 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from garfield_amd import _native
-from garfield_amd.ops import gar, selection
+from garfield_amd.ops import agr_attack, gar, selection
 from garfield_amd.parallel.comm import DistContext, all_gather_rows, collectives_on
-from garfield_amd.runtime.attacks import NEEDS_ESTIMATES, apply_attack
+from garfield_amd.runtime.attacks import AGR_ATTACKS, NEEDS_ESTIMATES, apply_attack
 from garfield_amd.utils.flat import FlatParams
 from garfield_amd.utils.profiling import PhaseTimer
 
@@ -213,6 +213,7 @@ class RobustDataParallel:
         self.cfg = cfg
         self.device = ctx.device
         self._check_pre_aggregation()
+        self._check_attacks()
         if not 0.0 <= cfg.worker_momentum < 1.0:
             raise ValueError(f"worker_momentum must satisfy 0 <= beta < 1, got {cfg.worker_momentum!r}")
         self.model = model.to(self.device)
@@ -259,7 +260,8 @@ class RobustDataParallel:
         self.local_slots = sorted(range(self.k), key=lambda j: (self.slot(j) in cfg.byzantine, j))
         self.step_count = 0
         self.last_weights = None
-        self._C = _native.require_for(self.device) if self.device.type == "cuda" else None
+        self.last_agr_gamma = {}   # adaptive attack kind -> the last step's γ (a one-element device tensor)
+        self._C =_native.require_for(self.device) if self.device.type == "cuda" else None
         self._one = torch.ones(1, dtype=torch.float32, device=self.device)
         self._gagg = torch.zeros(self.ld, dtype=torch.float32, device=self.device) \
             if cfg.gar in COORD_RULES else None
@@ -1019,8 +1021,35 @@ class RobustDataParallel:
         """Worker momentum, then the simulated Byzantine workers' rows (after the honest rows exist)."""
         self._finish_rows(0, self.d)
 
-    def _collude(self, rows, slots=None) -> None:
-        """The colluding attacks (lie, empire) on exchanged rows: ``rows[i]`` is (a
+    def _check_attacks(self) -> None:
+        """The adaptive attacks take at most MAX_ROWS estimate rows (peers + the targets of one kind)."""
+        kinds = [a for a in self.cfg.byzantine.values() if a in AGR_ATTACKS]
+        if not kinds:
+            return
+        n = self.cfg.workers_per_rank * self.ctx.world_size
+        honest = n - len(self.cfg.byzantine)
+        peers = honest if self.cfg.collusion == "all" else min(honest, max(len(self.cfg.byzantine) - 1, 0))
+        k = peers + max(kinds.count(a) for a in set(kinds))
+        if k > gar.MAX_ROWS:
+            raise ValueError(f"attack {kinds[0]!r}: at most {gar.MAX_ROWS} estimate rows (colluders' peers + targets), "
+                             f"got {k}")
+
+    def _agr_sets(self, slots) -> list:
+        """[(kind, peer indices, target indices)] of the adaptive attacks among the rows of ``slots``: the
+        estimates of a kind are the peers' rows (``cfg.collusion``, as for lie / empire) plus the honest
+        gradients of ALL its targets, and every target gets the same vector."""
+        byz = self.cfg.byzantine
+        if not any(a in AGR_ATTACKS for a in byz.values()):
+            return []
+        honest = [i for i, s in enumerate(slots) if s not in byz]
+        fw = sum(1 for s in slots if s in byz)
+        peers = honest if self.cfg.collusion == "all" else honest[: max(fw - 1, 0)]
+        kinds = sorted({byz[s] for s in slots if byz.get(s) in AGR_ATTACKS})
+        return [(kind, peers, [i for i, s in enumerate(slots) if byz.get(s) == kind]) for kind in kinds]
+
+    def _collude(self, rows, slots=None, agr: bool = True) -> None:
+        """The colluding attacks (lie, empire, and with ``agr`` the adaptive minmax / minsum kinds, which the
+        sharded step runs itself once every bucket has landed) on exchanged rows: ``rows[i]`` is (a
         coordinate slice of) the row of global slot ``slots[i]`` (default: i) and still
         holds that worker's honest gradient. Every rank holding the rows computes the
         same result (deterministic, coordinate-wise), so the sharded form (each owner on
@@ -1034,7 +1063,12 @@ class RobustDataParallel:
         if not byz:
             return
         slots = list(range(len(rows))) if slots is None else list(slots)
-        targets = [(i, byz[s]) for i, s in enumerate(slots) if byz.get(s) in NEEDS_ESTIMATES]
+        if agr:
+            # statistics, Gram, solve, write (ops/agr_attack.py), once per kind; a kind reads honest rows and
+            # its own targets only, so the kinds and lie / empire below do not see each other's output
+            for kind, peers, tg in self._agr_sets(slots):
+                self.last_agr_gamma[kind] = agr_attack.attack_rows([rows[i] for i in peers + tg], len(peers), kind)
+        targets = [(i, byz[s]) for i, s in enumerate(slots) if byz.get(s) in ("lie", "empire")]
         if not targets:
             return
         honest = [i for i, s in enumerate(slots) if s not in byz]

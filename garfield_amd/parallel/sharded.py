@@ -55,7 +55,7 @@ import torch
 import torch.distributed as dist
 
 from garfield_amd import _native
-from garfield_amd.ops import gar, selection
+from garfield_amd.ops import agr_attack, gar, selection
 from garfield_amd.parallel.comm import collectives_on, gloo_backend, world1_collectives
 from garfield_amd.parallel.engine import LAYERWISE_RULES, lw_job_ranges
 from garfield_amd.parallel.rccl import direct_backend
@@ -121,6 +121,7 @@ class _Bucket:
         self.rows: list = []
         self.gagg = None
         self.done = None
+        self.landed = False    # this step's rows are here and attacked (_wait ran)
 
 
 class ShardedAggregator:
@@ -283,6 +284,7 @@ class ShardedAggregator:
             with ctx:
                 e._finish_rows(b.lo, b.hi)
                 b.works = []
+                b.landed = False
                 if self._coll and self._rccl is not None:   # straight from the exchange rows
                     self._rccl.exchange(*b.p2p, self._comm_stream)
                 elif self._coll:
@@ -305,12 +307,43 @@ class ShardedAggregator:
         self._started = True
 
     def _wait(self, b: _Bucket) -> None:
+        if b.landed:     # the adaptive attacks' pass (_agr_collude) has been here
+            return
         for w in b.works:
             w.wait()
         b.works = []
         if b.done is not None:
             torch.cuda.current_stream(self.e.device).wait_event(b.done)   # main waits on comm: cheap
-        self.e._collude(b.rows)   # colluding attacks on this rank's coordinate shard of every row
+        # colluding attacks on this rank's coordinate shard of every row (lie / empire: coordinate-wise)
+        self.e._collude(b.rows, agr=False)
+        b.landed = True
+
+    def _agr_collude(self) -> None:
+        """The adaptive attacks (minmax / minsum) of the sharded step. γ needs every bucket of every rank,
+        so per bucket, as it lands and in bucket order, only the additive statistics of this rank's shard
+        are taken; the sums go through ONE small all-gather per kind (summed in rank order: the same bits on
+        every rank), the solve runs, and the write pass goes over each bucket's rows, all before the rule's
+        own Gram. lie / empire keep their per-bucket path (``_wait``)."""
+        e = self.e
+        sets = e._agr_sets(range(self.n))
+        if not sets:
+            return
+        sums = [None] * len(sets)
+        for b in self.buckets:
+            self._wait(b)
+            for i, (kind, peers, tg) in enumerate(sets):
+                g, p = agr_attack.agr_partials([b.rows[j] for j in peers + tg], agr_attack.parse(kind)[1])
+                sums[i] = [g, p] if sums[i] is None else [sums[i][0].add_(g), sums[i][1].add_(p)]
+        for (kind, peers, tg), (g, p) in zip(sets, sums):
+            objective, perturbation = agr_attack.parse(kind)
+            # one all-gather: the Gram widened to fp64 next to the fp64 statistics (fp32 Gram partials sum
+            # exactly enough in fp64 to round back to one fp32 value on every rank)
+            total = self._sum_over_ranks(torch.cat([g.double().reshape(-1), p]))
+            gram = total[:g.numel()].to(g.dtype).view(g.shape)
+            gamma = agr_attack.agr_gamma(gram, total[g.numel():], objective)
+            e.last_agr_gamma[kind] = gamma
+            for b in self.buckets:
+                agr_attack.agr_write([b.rows[j] for j in peers + tg], len(peers), gamma, perturbation)
 
     def _sum_over_ranks(self, t: torch.Tensor) -> torch.Tensor:
         """Every rank's ``t`` summed in rank order (identical result on every rank)."""
@@ -354,6 +387,7 @@ class ShardedAggregator:
         if not self._started:
             self.start_exchange()
         self._gathers = []
+        self._agr_collude()
         if cfg.layerwise and cfg.gar in LAYERWISE_RULES:   # per-tensor == flat for the coordinate rules
             self._layerwise(cfg, first)
         elif e.device.type == "cuda":

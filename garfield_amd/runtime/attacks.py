@@ -8,6 +8,8 @@ Differences, on purpose:
   ``masked_fill`` and discards the result, bug B3);
 * ``lie`` / ``empire`` take the colluders' gradient estimates as an argument
   instead of recomputing the honest gradient (bug B12 computed it twice);
+* ``minmax`` / ``minsum`` (``-uv``, ``-sgn``) are new: the adaptive attacks of the DnC paper,
+  on the same estimates, with gamma in closed form (docs/GAR_SEMANTICS.md);
 * extra ``nan`` / ``inf`` / ``zero`` attacks exercise the non-finite paths.
 
 All attacks return a new tensor of the input's dtype / device.
@@ -57,6 +59,22 @@ def empire_attack(grad: torch.Tensor, estimates=None, eps: float = EMPIRE_EPS, *
     return (-eps * E.mean(0)).to(grad.dtype)
 
 
+def _agr_attack(kind: str):
+    """Min-Max / Min-Sum (Shejwalkar & Houmansadr 2021): mu + gamma * p of the colluders' estimates with
+    the largest gamma that stays inside their distance ball, solved on their Gram matrix
+    (ops/agr_attack.py; suffix -uv / -sgn: the perturbation p, default -std)."""
+    def fn(grad: torch.Tensor, estimates=None, **_) -> torch.Tensor:
+        from garfield_amd.ops import agr_attack
+
+        return agr_attack.attack(_estimates(grad, estimates), kind).reshape(grad.shape).to(grad.dtype)
+    fn.__name__ = kind.replace("-", "_") + "_attack"
+    fn.__doc__ = _agr_attack.__doc__
+    return fn
+
+
+AGR_ATTACKS = ("minmax", "minmax-uv", "minmax-sgn", "minsum", "minsum-uv", "minsum-sgn")
+
+
 def nan_attack(grad: torch.Tensor, **_) -> torch.Tensor:
     return torch.full_like(grad, float("nan"))
 
@@ -78,13 +96,14 @@ WORKER_ATTACKS = {
     "nan": nan_attack,
     "inf": inf_attack,
     "zero": zero_attack,
+    **{kind: _agr_attack(kind) for kind in AGR_ATTACKS},
 }
 
 SERVER_ATTACKS = {"random": random_attack, "reverse": reverse_attack, "drop": drop_attack,
                   "nan": nan_attack, "zero": zero_attack}
 
 # attacks that need the colluding workers' gradient estimates
-NEEDS_ESTIMATES = {"lie", "empire"}
+NEEDS_ESTIMATES = {"lie", "empire", *AGR_ATTACKS}
 
 
 def apply_attack(name: str, grad: torch.Tensor, estimates=None, generator=None) -> torch.Tensor:

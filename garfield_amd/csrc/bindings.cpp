@@ -233,6 +233,40 @@ const at::Tensor& identity_rows(int n, const at::Device& dev) {
   return it->second;
 }
 
+// 16-bit averaged median of n <= 64 rows runs as Bulyan's tail with W = I (t = n); shared by
+// g_coordwise and coord_plan so both answer for the same launch
+bool averaged_median_reroute(int dt, int mode, int n) {
+  return mode == garfield::kAveragedMedian && dt != garfield::kF32 && n <= 64 && averaged_median_as_tail();
+}
+
+// What gpu_coordwise launches for (dtype, mode, n, d, f, beta, t): no GPU needed
+py::dict coord_plan(const py::object& dtype, int mode, int n, int64_t d, int f, int beta, int t) {
+  const std::string name = py::str(dtype);
+  int dt;
+  if (name == "torch.float32") dt = garfield::kF32;
+  else if (name == "torch.bfloat16") dt = garfield::kBF16;
+  else if (name == "torch.float16") dt = garfield::kF16;
+  else TORCH_CHECK(false, "coord_plan: dtype must be torch.float32, torch.bfloat16 or torch.float16, got ", name);
+  TORCH_CHECK(mode >= garfield::kMedian && mode <= garfield::kBulyanTail, "coord_plan: unknown mode ", mode);
+  TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows && d >= 0, "coord_plan: 1 <= n <= ", garfield::kMaxRows, ", d >= 0");
+  bool has_W = mode == garfield::kBulyanTail;
+  if (has_W) TORCH_CHECK(t >= 1 && t <= garfield::kMaxRows, "garfield: invalid t");
+  if (averaged_median_reroute(dt, mode, n)) {
+    mode = garfield::kBulyanTail;
+    t = n;
+    has_W = true;
+  }
+  const garfield::gpu::CoordPlanInfo pl = garfield::gpu::coordwise_plan(n, d, dt, mode, f, beta, t, has_W);
+  py::dict r;
+  r["family"] = pl.family;
+  r["np"] = pl.np;
+  r["grid"] = pl.grid;
+  r["coords_per_pass"] = pl.coords_per_pass;
+  r["sub"] = pl.sub;
+  r["bulyan"] = mode == garfield::kBulyanTail;
+  return r;
+}
+
 void g_coordwise(const RowSet& rs, int mode, int f, int beta, const c10::optional<at::Tensor>& W, int t,
                  uint64_t seed, double p, const at::Tensor& out) {
   check_gpu(rs);
@@ -244,7 +278,7 @@ void g_coordwise(const RowSet& rs, int mode, int f, int beta, const c10::optiona
     TORCH_CHECK(W.has_value() && W->numel() >= t * rs.n, "garfield: Bulyan tail needs W[t, n]");
     TORCH_CHECK(t >= 1 && t <= garfield::kMaxRows, "garfield: invalid t");
     w = fptr(*W);
-  } else if (mode == garfield::kAveragedMedian && rs.dt != garfield::kF32 && rs.n <= 64 && averaged_median_as_tail()) {
+  } else if (averaged_median_reroute(rs.dt, mode, rs.n)) {
     // the averaged median of the rows IS Bulyan's tail with W = I (t = n): the MFMA tail kernel
     // (set "means" = the rows themselves, exact) is ~1.5x faster than the direct window kernel
     // at n = 64 (profiles/r2/gar_bench_avgmed_tail.jsonl)
@@ -2206,6 +2240,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            [](const std::vector<at::Tensor>& L, int mode, int f, int beta, const c10::optional<at::Tensor>& W, int t,
               uint64_t seed, double p, const at::Tensor& o) { g_coordwise(rows_from_list(L, true), mode, f, beta, W, t, seed, p, o); },
            "Coordinate-wise rule (median / trimmed mean / averaged median / average-nan / condense / Bulyan tail)");
+  m.def("coord_plan", &coord_plan, py::arg("dtype"), py::arg("mode"), py::arg("n"), py::arg("d"), py::arg("f"),
+        py::arg("beta"), py::arg("t"),
+        "The kernel gpu_coordwise launches for these arguments (after its averaged-median reroute): "
+        "{family, np, grid, coords_per_pass (per workgroup: grid * coords_per_pass < d means the grid-stride "
+        "loop wraps), sub, bulyan}. Host only.");
   def_rows(m, "gpu_sqdist",
            [](const at::Tensor& G, const at::Tensor& c, const at::Tensor& s) { g_sqdist(rows_from_2d(G, true), c, s); },
            [](const std::vector<at::Tensor>& L, const at::Tensor& c, const at::Tensor& s) { g_sqdist(rows_from_list(L, true), c, s); },

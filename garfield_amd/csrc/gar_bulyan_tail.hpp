@@ -19,6 +19,8 @@
 // sort by distance, unlike the generic closest_mean).
 #pragma once
 #include <cstdlib>
+#include <stdexcept>
+#include "gar_coord_plan.hpp"
 #include "gar_device.hpp"
 
 namespace garfield {
@@ -69,9 +71,8 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
   return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
-constexpr int kTailTile = 256;
-constexpr int kTailMaxExcluded = 16;  // e = t - beta <= 16 (host checks; larger e: generic kernel)
-
+// kTailTile = 256 coordinates per tile; e = t - beta <= kTailMaxExcluded = 16 (coord::plan
+// checks; larger e: generic kernel)
 template <int DT, int NP, bool DIRECT>
 __global__ __launch_bounds__(256) void k_bulyan_tail(RowTable rows, int n, int64_t d, int beta,
                                                      const float* __restrict__ W, int t, void* out, int out_dt) {
@@ -189,29 +190,16 @@ __global__ __launch_bounds__(256) void k_bulyan_tail(RowTable rows, int n, int64
   }
 }
 
-// grid cap of the tail kernels (grid-stride over coordinate groups); GARFIELD_TAIL_GRID overrides
-inline int64_t tail_grid_cap(int64_t dflt) {
-  static const int64_t env = [] {
-    const char* e = std::getenv("GARFIELD_TAIL_GRID");
-    const long v = e ? std::atol(e) : 0;
-    return static_cast<int64_t>(v > 0 ? v : 0);
-  }();
-  return env > 0 ? env : dflt;
-}
-
-// W == nullptr: averaged median of the n rows themselves (t = n)
+// tail_window_direct: averaged median of the n rows themselves (t = n, no W)
 template <int DT, int NP>
-void launch_bulyan_tail(const RowTable& rows, int n, int64_t d, int beta, const float* W, int t, void* out,
-                        int out_dt, hipStream_t s) {
-  int64_t g = d / kTailTile + 1;
-  const int64_t cap = tail_grid_cap(4096);
-  if (g > cap) g = cap;
-  if (W == nullptr)
-    hipLaunchKernelGGL((k_bulyan_tail<DT, NP, true>), dim3(static_cast<unsigned>(g)), dim3(256), 0, s, rows, n, d,
-                       beta, W, n, out, out_dt);
+void launch_bulyan_tail(const Plan& pl, const RowTable& rows, int n, int64_t d, int beta, const float* W, int t,
+                        void* out, int out_dt, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(pl.grid)), block(256);
+  if (pl.family == kFamTailWindowDirect)
+    hipLaunchKernelGGL((k_bulyan_tail<DT, NP, true>), grid, block, 0, s, rows, n, d, beta,
+                       static_cast<const float*>(nullptr), n, out, out_dt);
   else
-    hipLaunchKernelGGL((k_bulyan_tail<DT, NP, false>), dim3(static_cast<unsigned>(g)), dim3(256), 0, s, rows, n, d,
-                       beta, W, t, out, out_dt);
+    hipLaunchKernelGGL((k_bulyan_tail<DT, NP, false>), grid, block, 0, s, rows, n, d, beta, W, t, out, out_dt);
 }
 
 // ---------------------------------------------------------------------------
@@ -279,7 +267,7 @@ __device__ __forceinline__ void oem_sort_f32(float (&v)[NP]) {
 // back at uniform addresses -- no select chains over the register array. The e
 // lowest stay in registers (static indices). EXACT: inputs may hold +-inf (NaN
 // already mapped to +inf), so distances are sanitised like the reference's.
-constexpr int wm_p0(int np) { return (np / 4) & ~3; }
+// (wm_p0: gar_coord_plan.hpp, where coord::plan checks the two positions.)
 
 template <int NP, bool EXACT>
 __device__ __forceinline__ float window_mean(float (&v)[NP], int tt, int bb, float inv_beta, float* ks, int lane) {
@@ -539,17 +527,13 @@ __global__ __launch_bounds__(256, 2) void k_bulyan_tail_mfma(RowTable rows, int 
 }
 
 template <int DT, int NP>
-void launch_tail_mfma_ks(int ks, const RowTable& rows, int n, int64_t groups, int last_width, int beta,
+void launch_tail_mfma_ks(const Plan& pl, const RowTable& rows, int n, int64_t groups, int last_width, int beta,
                          const float* W, int t, void* out, int out_dt, hipStream_t s) {
-  int64_t g = (groups + 3) / 4;
-  const int64_t cap = tail_grid_cap(4096);
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  const dim3 grid(static_cast<unsigned>(g)), block(256);
+  const dim3 grid(static_cast<unsigned>(pl.grid)), block(256);
 #define GARFIELD_TAIL_MFMA(KS)                                                                                   \
   hipLaunchKernelGGL((k_bulyan_tail_mfma<DT, NP, KS>), grid, block, 0, s, rows, n, groups, last_width, beta, W, t, \
                      out, out_dt)
-  switch (ks) {
+  switch (pl.sub) {
     case 1: GARFIELD_TAIL_MFMA(1); break;
     case 2: GARFIELD_TAIL_MFMA(2); break;
     case 3: GARFIELD_TAIL_MFMA(3); break;
@@ -558,30 +542,27 @@ void launch_tail_mfma_ks(int ks, const RowTable& rows, int n, int64_t groups, in
 #undef GARFIELD_TAIL_MFMA
 }
 
-// bf16/fp16, n <= 64, t <= 64, e = t - beta <= 16: the MFMA tail (every coordinate,
-// the d % 64 tail in its exact pass); otherwise false (generic kernels)
+// The MFMA tail (every coordinate, the d % 64 tail in its exact pass). coord::plan names it for
+// bf16/fp16, n <= 64, t <= 64, e = t - beta <= 16 and window_mean's spilled positions (t / 2,
+// beta >= wm_p0); pl.np <= 64 sets, pl.sub k-steps.
 template <int DT>
-bool launch_bulyan_tail_mfma(const RowTable& rows, int n, int64_t d, int beta, const float* W, int t, void* out,
-                             int out_dt, hipStream_t s) {
-  if (DT == kF32 || n > 64 || t > 64 || t < 1 || beta < 1 || t - beta > kTailMaxExcluded || W == nullptr) return false;
-  const int np = t <= 8 ? 8 : (t <= 16 ? 16 : (t <= 32 ? 32 : 64));
-  if (t / 2 < wm_p0(np) || beta < wm_p0(np)) return false;   // window_mean's spilled positions
+void launch_bulyan_tail_mfma(const Plan& pl, const RowTable& rows, int n, int64_t d, int beta, const float* W, int t,
+                             void* out, int out_dt, hipStream_t s) {
   const int64_t groups = d / 64;
   const int last = static_cast<int>(d - groups * 64);
-  const int ks = (n + 15) / 16;
-  switch (np) {
-    case 8: launch_tail_mfma_ks<DT, 8>(ks, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
-    case 16: launch_tail_mfma_ks<DT, 16>(ks, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
-    case 32: launch_tail_mfma_ks<DT, 32>(ks, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
-    default: launch_tail_mfma_ks<DT, 64>(ks, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
+  switch (pl.np) {
+    case 8: launch_tail_mfma_ks<DT, 8>(pl, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
+    case 16: launch_tail_mfma_ks<DT, 16>(pl, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
+    case 32: launch_tail_mfma_ks<DT, 32>(pl, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
+    case 64: launch_tail_mfma_ks<DT, 64>(pl, rows, n, groups, last, beta, W, t, out, out_dt, s); break;
+    default: throw std::logic_error("garfield: the MFMA tail holds at most 64 sets");
   }
-  return true;
 }
 
-// fp32, n <= 64, t <= 64, e = t - beta <= 16: the register kernel of gar_tail_f32.hip; otherwise false
-// (generic kernels)
-bool launch_bulyan_tail_f32(const RowTable& rows, int n, int64_t d, int beta, const float* W, int t, void* out,
-                            int out_dt, hipStream_t s);
+// The fp32 register kernel of gar_tail_f32.hip: coord::plan names it under the MFMA tail's
+// limits on fp32 rows; pl.np <= 64 sets, pl.sub padded rows.
+void launch_bulyan_tail_f32(const Plan& pl, const RowTable& rows, int n, int64_t d, int beta, const float* W, int t,
+                            void* out, int out_dt, hipStream_t s);
 
 }  // namespace coord
 }  // namespace gpu

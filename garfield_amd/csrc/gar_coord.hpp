@@ -2,6 +2,8 @@
 // mode in gar_coord_m*.hip so the 90 variants compile in parallel.
 #pragma once
 #include <cstdlib>
+#include <stdexcept>
+#include "gar_coord_plan.hpp"
 #include "gar_device.hpp"
 
 namespace garfield {
@@ -180,36 +182,6 @@ __global__ __launch_bounds__(256) void k_coordwise(RowTable rows, int n, int64_t
   }
 }
 
-// knobs: GARFIELD_COORD16=0 disables the packed 16-bit-key kernels (A/B runs);
-// GARFIELD_COORD16_GRID caps their grid (grid-stride loop beyond it)
-inline bool coord16_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("GARFIELD_COORD16");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-inline bool coord_mfma_tail_enabled() {  // GARFIELD_MFMA_TAIL=0: Bulyan tail without MFMA (A/B runs)
-  static const bool on = [] {
-    const char* e = std::getenv("GARFIELD_MFMA_TAIL");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-// Grid cap of the packed 16-bit coordinate kernels (grid-stride loop). Measured at d = 23.5M
-// bf16 (profiles/r2/coord16_grid_sweep.log): small sets (NP <= 16, 8 coordinates per lane) are
-// fastest with one pass per lane (cap 16384: median n=8 0.080 vs 0.084 ms at 4096); large sets
-// with 4096 (n=64 0.611 vs 0.634 ms at 16384). GARFIELD_COORD16_GRID overrides both.
-inline int64_t coord16_grid_cap(int np) {
-  static const int64_t env = [] {
-    const char* e = std::getenv("GARFIELD_COORD16_GRID");
-    const long v = e ? std::atol(e) : 0;
-    return static_cast<int64_t>(v > 0 ? v : 0);
-  }();
-  if (env > 0) return env;
-  return np <= 16 ? 16384 : 4096;
-}
-
 }  // namespace coord
 }  // namespace gpu
 }  // namespace garfield
@@ -224,8 +196,7 @@ namespace coord {
 // Large n (NP >= 32): one lane per coordinate would issue n 2-byte loads; instead
 // a workgroup stages a [n x 256-coordinate] tile through LDS with 16-byte loads
 // (each row segment is 512 B / 1 KB contiguous), then every lane reads its
-// column (conflict-free: consecutive lanes, consecutive elements).
-constexpr int kCoordTile = 256;
+// column (conflict-free: consecutive lanes, consecutive elements). Tile: kCoordTile coordinates.
 
 template <int DT, int NP, int MODE>
 __global__ __launch_bounds__(256) void k_coordwise_lds(RowTable rows, int n, int64_t d, int f, int beta,
@@ -299,74 +270,74 @@ __global__ __launch_bounds__(256) void k_coordwise_lds(RowTable rows, int n, int
   }
 }
 
+// Launches what coord::plan chose (gar_coord_plan.hpp holds every run-time condition). The
+// `if constexpr` guards only keep kernels that no plan can name for this (DT, NP, MODE) from
+// being instantiated; a plan outside them is an error, never a fall-through to another kernel.
 template <int DT, int NP, int VEC, int MODE>
-void launch_coord(const RowTable& rows, int n, int64_t d, int f, int beta, const float* W, int t, uint64_t seed,
-                  uint64_t thr, void* out, int out_dt, hipStream_t s) {
+void launch_coord(const Plan& pl, const RowTable& rows, int n, int64_t d, int f, int beta, const float* W, int t,
+                  uint64_t seed, uint64_t thr, void* out, int out_dt, hipStream_t s) {
+  static_assert(VEC == coord_vec(NP), "coord::plan's VEC");
   constexpr int ESZ = (DT == kF32) ? 4 : 2;
-  if constexpr (DT != kF32 && coord16_mode<MODE>()) {
-    if (coord16_enabled()) {
-      launch_coord16<DT, NP, MODE>(rows, n, d, f, beta, seed, thr, out, out_dt, s);
+  const dim3 grid(static_cast<unsigned>(pl.grid)), block(256);
+  if constexpr (DT != kF32 && coord16_mode(MODE)) {
+    if (pl.family == kFamCoord16) {
+      launch_coord16<DT, NP, MODE>(pl, rows, n, d, f, beta, seed, thr, out, out_dt, s);
       return;
     }
   }
   if constexpr (MODE == kBulyanTail && DT != kF32) {
-    if (n <= 64 && coord16_enabled() && coord_mfma_tail_enabled() &&
-        launch_bulyan_tail_mfma<DT>(rows, n, d, beta, W, t, out, out_dt, s))
+    if (pl.family == kFamTailMfma) {
+      launch_bulyan_tail_mfma<DT>(pl, rows, n, d, beta, W, t, out, out_dt, s);
       return;
+    }
   }
   if constexpr (MODE == kBulyanTail && DT == kF32) {
-    if (n <= 64 && coord16_enabled() && launch_bulyan_tail_f32(rows, n, d, beta, W, t, out, out_dt, s)) return;
+    if (pl.family == kFamTailF32) {
+      launch_bulyan_tail_f32(pl, rows, n, d, beta, W, t, out, out_dt, s);
+      return;
+    }
   }
   if constexpr ((MODE == kBulyanTail || MODE == kAveragedMedian) && NP <= 64) {
-    const int tt = MODE == kBulyanTail ? t : n;
-    if (n <= 64 && tt - beta <= kTailMaxExcluded && coord16_enabled()) {
-      launch_bulyan_tail<DT, NP>(rows, n, d, beta, MODE == kBulyanTail ? W : nullptr, t, out, out_dt, s);
+    if (pl.family == kFamTailWindow || pl.family == kFamTailWindowDirect) {
+      launch_bulyan_tail<DT, NP>(pl, rows, n, d, beta, W, t, out, out_dt, s);
       return;
     }
   }
-  // LDS-staged path: NP >= 32, tile <= 64 KB, and (Bulyan tail) all n rows fit the NP-row tile
   if constexpr (NP >= 32 && NP * kCoordTile * ESZ <= 65536) {
-    if (MODE != kBulyanTail || n <= NP) {
-      int64_t g = d / kCoordTile;
-      if (g < 1) g = 1;
-      if (g > 2048) g = 2048;
-      hipLaunchKernelGGL((k_coordwise_lds<DT, NP, MODE>), dim3(static_cast<unsigned>(g)), dim3(256), 0, s, rows, n,
-                         d, f, beta, W, t, seed, thr, out, out_dt);
+    if (pl.family == kFamCoordwiseLds) {
+      hipLaunchKernelGGL((k_coordwise_lds<DT, NP, MODE>), grid, block, 0, s, rows, n, d, f, beta, W, t, seed, thr,
+                         out, out_dt);
       return;
     }
   }
-  int64_t g = (d / VEC + 255) / 256;
-  if (g < 1) g = 1;
-  if (g > 4096) g = 4096;
-  hipLaunchKernelGGL((k_coordwise<DT, NP, VEC, MODE>), dim3(static_cast<unsigned>(g)), dim3(256), 0, s, rows, n, d,
-                     f, beta, W, t, seed, thr, out, out_dt);
+  if (pl.family != kFamCoordwise) throw std::logic_error("garfield: coord::plan named a kernel this shape has not");
+  hipLaunchKernelGGL((k_coordwise<DT, NP, VEC, MODE>), grid, block, 0, s, rows, n, d, f, beta, W, t, seed, thr, out,
+                     out_dt);
 }
 
 template <int DT, int MODE>
-void coord_np(int np, const RowTable& rows, int n, int64_t d, int f, int beta, const float* W, int t, uint64_t seed,
-              uint64_t thr, void* out, int out_dt, hipStream_t s) {
-  switch (np) {
-    case 8: launch_coord<DT, 8, 8, MODE>(rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
-    case 16: launch_coord<DT, 16, 4, MODE>(rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
-    case 32: launch_coord<DT, 32, 2, MODE>(rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
-    case 64: launch_coord<DT, 64, 1, MODE>(rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
-    default: launch_coord<DT, 128, 1, MODE>(rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
+void coord_np(const Plan& pl, const RowTable& rows, int n, int64_t d, int f, int beta, const float* W, int t,
+              uint64_t seed, uint64_t thr, void* out, int out_dt, hipStream_t s) {
+  switch (pl.np) {
+    case 8: launch_coord<DT, 8, 8, MODE>(pl, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
+    case 16: launch_coord<DT, 16, 4, MODE>(pl, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
+    case 32: launch_coord<DT, 32, 2, MODE>(pl, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
+    case 64: launch_coord<DT, 64, 1, MODE>(pl, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
+    default: launch_coord<DT, 128, 1, MODE>(pl, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s); break;
   }
 }
 
-inline int np_for(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : (k <= 32 ? 32 : (k <= 64 ? 64 : 128))); }
-
 template <int MODE> struct ByDtype {
   template <int DT> struct F {
-    static void run(int np, const RowTable& rows, int n, int64_t d, int f, int beta, const float* W, int t,
+    static void run(const Plan& pl, const RowTable& rows, int n, int64_t d, int f, int beta, const float* W, int t,
                     uint64_t seed, uint64_t thr, void* out, int out_dt, hipStream_t s) {
-      coord_np<DT, MODE>(np, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s);
+      coord_np<DT, MODE>(pl, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s);
     }
   };
 };
 
 template <int MODE>
-void coord_mode(int dt, int np, const RowTable& rows, int n, int64_t d, int f, int beta, const float* W,
+void coord_mode(int dt, const Plan& pl, const RowTable& rows, int n, int64_t d, int f, int beta, const float* W,
                 int t, uint64_t seed, uint64_t thr, void* out, int out_dt, hipStream_t s);
 
 }  // namespace coord

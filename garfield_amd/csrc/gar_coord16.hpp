@@ -20,6 +20,7 @@
 // bulyan.cu:227-243 / deprecated_native native.cpp:714-747 (averaged median),
 // plus the trimmed mean (not in the reference).
 #pragma once
+#include "gar_coord_plan.hpp"
 #include "gar_device.hpp"
 
 namespace garfield {
@@ -288,22 +289,14 @@ __global__ __launch_bounds__(256) void k_coord16(RowTable rows, int n, int64_t d
   }
 }
 
-template <int NP> struct Coord16Words { static constexpr int P = NP <= 16 ? 4 : (NP == 32 ? 2 : 1); };
-
-template <int MODE> constexpr bool coord16_mode() {
-  return MODE == kMedian || MODE == kTrimmedMean || MODE == kCondense;  // averaged median: gar_bulyan_tail.hpp
-}
-
+// words per row P = coord16_words(NP) and the modes (coord16_mode; the averaged median runs on
+// gar_bulyan_tail.hpp) are coord::plan's, gar_coord_plan.hpp
 template <int DT, int NP, int MODE>
-void launch_coord16(const RowTable& rows, int n, int64_t d, int f, int beta, uint64_t seed, uint64_t thr, void* out,
-                    int out_dt, hipStream_t s) {
-  constexpr int P = Coord16Words<NP>::P;
-  int64_t g = (d / (2 * P) + 255) / 256;
-  const int64_t cap = coord16_grid_cap(NP);
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL((k_coord16<DT, NP, P, MODE>), dim3(static_cast<unsigned>(g)), dim3(256), 0, s, rows, n, d, f,
-                     beta, seed, thr, out, out_dt);
+void launch_coord16(const Plan& pl, const RowTable& rows, int n, int64_t d, int f, int beta, uint64_t seed,
+                    uint64_t thr, void* out, int out_dt, hipStream_t s) {
+  constexpr int P = coord16_words(NP);
+  hipLaunchKernelGGL((k_coord16<DT, NP, P, MODE>), dim3(static_cast<unsigned>(pl.grid)), dim3(256), 0, s, rows, n, d,
+                     f, beta, seed, thr, out, out_dt);
 }
 
 }  // namespace coord

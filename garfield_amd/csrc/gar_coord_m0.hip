@@ -6,10 +6,10 @@ namespace gpu {
 namespace coord {
 
 template <>
-void coord_mode<kMedian>(int dt, int np, const RowTable& rows, int n, int64_t d, int f, int beta,
+void coord_mode<kMedian>(int dt, const Plan& pl, const RowTable& rows, int n, int64_t d, int f, int beta,
                        const float* W, int t, uint64_t seed, uint64_t thr, void* out, int out_dt,
                        hipStream_t s) {
-  by_dtype<ByDtype<kMedian>::F>(dt, np, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s);
+  by_dtype<ByDtype<kMedian>::F>(dt, pl, rows, n, d, f, beta, W, t, seed, thr, out, out_dt, s);
 }
 
 }  // namespace coord

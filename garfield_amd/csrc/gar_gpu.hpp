@@ -120,6 +120,17 @@ void coordwise(const RowTable& rows, int n, int64_t d, int dt, int mode, int f, 
                const float* W, int t, uint64_t seed, uint64_t threshold, void* out,
                int out_dt, hipStream_t stream);
 int coordwise_max_rows();
+// What coordwise() launches for these arguments (coord::plan of gar_coord_plan.hpp; host only, no
+// GPU needed): the kernel family by name, its padded row count, grid, the coordinates one
+// workgroup covers per pass of its grid-stride loop, and the family's second template choice.
+struct CoordPlanInfo {
+  const char* family;
+  int np;
+  int64_t grid;
+  int64_t coords_per_pass;
+  int sub;
+};
+CoordPlanInfo coordwise_plan(int n, int64_t d, int dt, int mode, int f, int beta, int t, bool has_W);
 
 // ---- Large gradient sets (kMaxRows < n <= kLargeRows), one [n, ld] matrix (gar_large.hip) ----
 // out[j] = Σ_i w[i] x[i, j] (out in x's dtype); mode 0 median, 1 trimmed-mean(f), 2 averaged-median(beta).

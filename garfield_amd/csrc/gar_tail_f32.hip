@@ -98,16 +98,12 @@ __global__ __launch_bounds__(256) void k_bulyan_tail_f32(RowTable rows, int n, i
 }
 
 template <int NP>
-void launch_tail_f32_nr(int nr, const RowTable& rows, int n, int64_t d, int beta, const float* W, int t, void* out,
-                        int out_dt, hipStream_t s) {
-  int64_t g = ((d + 63) / 64 + 3) / 4;
-  const int64_t cap = tail_grid_cap(2048);
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
+void launch_tail_f32_nr(const Plan& pl, const RowTable& rows, int n, int64_t d, int beta, const float* W, int t,
+                        void* out, int out_dt, hipStream_t s) {
+  const dim3 grid(static_cast<unsigned>(pl.grid));
 #define GARFIELD_TAIL_F32(NRV)                                                                                     \
-  hipLaunchKernelGGL((k_bulyan_tail_f32<NP, NRV>), dim3(static_cast<unsigned>(g)), dim3(256), 0, s, rows, n, d, beta, \
-                     W, t, out, out_dt)
-  switch (nr) {
+  hipLaunchKernelGGL((k_bulyan_tail_f32<NP, NRV>), grid, dim3(256), 0, s, rows, n, d, beta, W, t, out, out_dt)
+  switch (pl.sub) {
     case 16: GARFIELD_TAIL_F32(16); break;
     case 32: GARFIELD_TAIL_F32(32); break;
     default: GARFIELD_TAIL_F32(64); break;
@@ -115,21 +111,17 @@ void launch_tail_f32_nr(int nr, const RowTable& rows, int n, int64_t d, int beta
 #undef GARFIELD_TAIL_F32
 }
 
-// fp32, n <= 64, t <= 64, e = t - beta <= 16 (window_mean's layout, as the MFMA tail): the register
-// kernel; otherwise false (generic kernels)
-bool launch_bulyan_tail_f32(const RowTable& rows, int n, int64_t d, int beta, const float* W, int t, void* out,
-                                   int out_dt, hipStream_t s) {
-  if (n > 64 || t > 64 || t < 1 || beta < 1 || t - beta > kTailMaxExcluded || W == nullptr || d < 1) return false;
-  const int np = t <= 8 ? 8 : (t <= 16 ? 16 : (t <= 32 ? 32 : 64));
-  if (t / 2 < wm_p0(np) || beta < wm_p0(np)) return false;
-  const int nr = n <= 16 ? 16 : (n <= 32 ? 32 : 64);
-  switch (np) {
-    case 8: launch_tail_f32_nr<8>(nr, rows, n, d, beta, W, t, out, out_dt, s); break;
-    case 16: launch_tail_f32_nr<16>(nr, rows, n, d, beta, W, t, out, out_dt, s); break;
-    case 32: launch_tail_f32_nr<32>(nr, rows, n, d, beta, W, t, out, out_dt, s); break;
-    default: launch_tail_f32_nr<64>(nr, rows, n, d, beta, W, t, out, out_dt, s); break;
+// fp32, n <= 64, t <= 64, e = t - beta <= 16 (window_mean's layout, as the MFMA tail): coord::plan
+// names this register kernel then
+void launch_bulyan_tail_f32(const Plan& pl, const RowTable& rows, int n, int64_t d, int beta, const float* W, int t,
+                            void* out, int out_dt, hipStream_t s) {
+  switch (pl.np) {
+    case 8: launch_tail_f32_nr<8>(pl, rows, n, d, beta, W, t, out, out_dt, s); break;
+    case 16: launch_tail_f32_nr<16>(pl, rows, n, d, beta, W, t, out, out_dt, s); break;
+    case 32: launch_tail_f32_nr<32>(pl, rows, n, d, beta, W, t, out, out_dt, s); break;
+    case 64: launch_tail_f32_nr<64>(pl, rows, n, d, beta, W, t, out, out_dt, s); break;
+    default: throw std::logic_error("garfield: the fp32 tail holds at most 64 sets");
   }
-  return true;
 }
 
 }  // namespace coord

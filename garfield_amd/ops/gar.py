@@ -255,7 +255,10 @@ def pairwise_distances(gradients) -> torch.Tensor:
 def combine(gradients, weights: torch.Tensor) -> torch.Tensor:
     rows = prepare(gradients)
     if _large(rows):
-        return _large_combine(rows, weights)
+        X = _matrix(rows)
+        out = torch.empty(rows.d, dtype=X.dtype, device=X.device)
+        _native.native().gpu_large_combine(X, weights.to(X.device, torch.float32).contiguous(), out)
+        return _finish(out, rows)
     if rows.n > MAX_ROWS:
         return _finish((weights.to(rows.device, torch.float32)[:, None] * rows.stacked().float()).sum(0), rows)
     C = _C_for(rows)
@@ -292,13 +295,6 @@ def _matrix(rows: Rows) -> torch.Tensor:
     return X if X.stride(1) == 1 else X.contiguous()
 
 
-def _large_combine(rows: Rows, w: torch.Tensor) -> torch.Tensor:
-    X = _matrix(rows)
-    out = torch.empty(rows.d, dtype=X.dtype, device=X.device)
-    _native.native().gpu_large_combine(X, w.to(X.device, torch.float32).contiguous(), out)
-    return _finish(out, rows)
-
-
 # --------------------------------------------------------------------------- #
 # Rules
 
@@ -306,17 +302,14 @@ def _large_combine(rows: Rows, w: torch.Tensor) -> torch.Tensor:
 def average(gradients, **_) -> torch.Tensor:
     rows = prepare(gradients)
     if rows.device.type == "cuda" and rows.n <= MAX_ROWS:
-        C = _C_for(rows)
         ws = workspace(rows)
         w = ws.tensors.get("avg_w")
         if w is None:
             w = torch.full((rows.n,), 1.0 / rows.n, dtype=torch.float32, device=rows.device)
             ws.tensors["avg_w"] = w
-        out = torch.empty(rows.d, dtype=rows.dtype, device=rows.device)
-        C.gpu_combine(rows.obj, w, out)
-        return _finish(out, rows)
+        return combine(rows, w)
     if _large(rows):
-        return _large_combine(rows, torch.full((rows.n,), 1.0 / rows.n, dtype=torch.float32, device=rows.device))
+        return combine(rows, torch.full((rows.n,), 1.0 / rows.n, dtype=torch.float32, device=rows.device))
     return _finish(rows.stacked().float().mean(0) if rows.dtype != torch.float64 else rows.stacked().mean(0), rows)
 
 
@@ -349,22 +342,7 @@ def krum_weights(gradients, f: int, m: int | None = None, pre: str | None = None
 
 def krum(gradients, f: int, m: int | None = None, **_) -> torch.Tensor:
     rows = prepare(gradients)
-    return _combine_rows(rows, krum_weights(rows, f, m))
-
-
-def _combine_rows(rows: Rows, w: torch.Tensor) -> torch.Tensor:
-    if _large(rows):
-        return _large_combine(rows, w)
-    if rows.n > MAX_ROWS:
-        return _finish((w.to(rows.device)[:, None] * rows.stacked().float()).sum(0), rows)
-    C = _C_for(rows)
-    if rows.device.type == "cuda":
-        out = torch.empty(rows.d, dtype=rows.dtype, device=rows.device)
-        C.gpu_combine(rows.obj, w, out)
-        return _finish(out, rows)
-    if C is None:
-        return ref.combine(rows.stacked(), w.double()).to(rows.out_dtype)
-    return _finish(C.cpu_combine(rows.obj, w), rows)
+    return combine(rows, krum_weights(rows, f, m))
 
 
 def geomed_weights(gradients, iters: int = 32, nu: float = 1e-6, pre: str | None = None, f: int = 0) -> torch.Tensor:
@@ -379,7 +357,7 @@ def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> tor
     """Geometric median (minimiser of the sum of L2 distances; breakdown point 1/2, so ``f`` only
     enters the registry's check): Σ_i a_i g_i with the weights of :func:`geomed_weights`."""
     rows = prepare(gradients)
-    return _combine_rows(rows, geomed_weights(rows, iters, nu))
+    return combine(rows, geomed_weights(rows, iters, nu))
 
 
 # DnC spectral filtering (docs/GAR_SEMANTICS.md): the squared projection of every centred row on the top
@@ -400,7 +378,7 @@ def dnc(gradients, f: int = 0, m: int | None = None, iters: int = 16, **_) -> to
     """DnC spectral filtering (Shejwalkar & Houmansadr, 2021; all coordinates, one filter): the average
     of the rows kept by :func:`dnc_weights`."""
     rows = prepare(gradients)
-    return _combine_rows(rows, dnc_weights(rows, f, m, iters))
+    return combine(rows, dnc_weights(rows, f, m, iters))
 
 
 # Centered clipping (CC; docs/GAR_SEMANTICS.md): v <- v + (1/n) Σ_i (x_i - v) min(1, tau / ||x_i - v||). The
@@ -451,7 +429,7 @@ def cclip(gradients, f: int = 0, tau: float | None = None, iters: int = 3, start
     """Centered clipping (Karimireddy et al., 2021): Σ_i a_i g_i (+ a_n center) with the weights of
     :func:`cclip_weights`."""
     rows, w = _cclip_rows_w(gradients, f, tau, iters, start, center, m, pre)
-    return _combine_rows(rows, w)
+    return combine(rows, w)
 
 
 # Nearest-neighbour mixing (NNM; docs/GAR_SEMANTICS.md): every row is replaced by the mean of its
@@ -504,7 +482,7 @@ def nnm_weights(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
 def nnm(gradients, f: int, rule: str = "krum", **kw) -> torch.Tensor:
     """``rule`` after nearest-neighbour mixing: Σ_j w_j g_j with the weights of :func:`nnm_weights`."""
     rows = prepare(gradients)
-    return _combine_rows(rows, nnm_weights(rows, f, rule, **kw))
+    return combine(rows, nnm_weights(rows, f, rule, **kw))
 
 
 # NNM before a coordinate-wise rule (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing before a
@@ -605,80 +583,161 @@ def bulyan_weights(gradients, f: int, m: int | None = None) -> torch.Tensor:
     return selection_weights(rows, resolve("bulyan", rows.n, f, m))
 
 
+def bulyan_sizes(n: int, f: int) -> tuple:
+    """(t, beta) of Bulyan over n rows: t = n - 2f - 2 selection rounds, then per coordinate the mean of
+    the beta = t - 2f selection means closest to their median."""
+    t = n - 2 * f - 2
+    return t, t - 2 * f
+
+
+def bulyan_tail_into(C, rows, W: torch.Tensor, n: int, f: int, out: torch.Tensor, jobs=None) -> torch.Tensor:
+    """``out`` = Bulyan's tail over device rows (n <= MAX_ROWS) with the selection weights ``W`` [t, n]; with
+    a job table ``jobs`` the segmented tail (gar_layerwise.hip), each job with its segment's W of [L, t, n]."""
+    t, beta = bulyan_sizes(n, f)
+    if jobs is not None:
+        C.gpu_lw_bulyan_tail(rows, jobs, W, t, beta, out)
+    else:
+        C.gpu_coordwise(rows, _MODE["bulyan-tail"], f, beta, W.reshape(-1), t, 0, 1.0, out)
+    return out
+
+
+def bulyan_tail_large(V: torch.Tensor, n: int, f: int, out: torch.Tensor) -> torch.Tensor:
+    """``out`` = Bulyan's tail of the selection means ``V`` = W·X [t, d'] (fp32, GPU): their averaged median."""
+    _native.native().gpu_large_coord(V, _LARGE_MODE["averaged-median"], 0, bulyan_sizes(n, f)[1], out)
+    return out
+
+
+def bulyan_tail_host(C, X: torch.Tensor, W: torch.Tensor, n: int, f: int) -> torch.Tensor:
+    """Bulyan's tail over CPU rows ``X`` [n, d'] with ``W`` [t, n]: the C++ function, else torch."""
+    t, beta = bulyan_sizes(n, f)
+    if C is not None:
+        return C.cpu_coordwise(X, _MODE["bulyan-tail"], f, beta, W.reshape(-1), t, 0, 1.0)
+    return _torch_closest_mean(W @ X, beta)
+
+
 def bulyan(gradients, f: int, m: int | None = None, **_) -> torch.Tensor:
     rows = prepare(gradients)
-    m = rows.n - f - 2 if m is None else m
-    t = rows.n - 2 * f - 2
-    beta = t - 2 * f
+    n = rows.n
+    m = n - f - 2 if m is None else m
+    t, beta = bulyan_sizes(n, f)
     W = bulyan_weights(rows, f, m)
     if _large(rows):   # V = W·X column chunk by chunk (bounded fp32 memory), then the radix-select tail
         X, Wd = _matrix(rows), W.to(rows.device, torch.float32)
         out = torch.empty(rows.d, dtype=torch.float32, device=rows.device)
-        step = max(1, (1 << 28) // (4 * max(rows.n, t)))
+        step = max(1, (1 << 28) // (4 * max(n, t)))
         Vbuf = torch.empty((t, min(step, rows.d)), dtype=torch.float32, device=rows.device)
         for c0 in range(0, rows.d, step):
             w = min(step, rows.d - c0)
-            V = large_wx(Wd, X[:, c0:c0 + w], Vbuf[:, :w])
-            _native.native().gpu_large_coord(V, 2, 0, beta, out[c0:c0 + w])
+            bulyan_tail_large(large_wx(Wd, X[:, c0:c0 + w], Vbuf[:, :w]), n, f, out[c0:c0 + w])
         return _finish(out, rows)
-    if rows.n > MAX_ROWS:
+    if n > MAX_ROWS:
         V = W.to(rows.device) @ rows.stacked().float()
         return _finish(_torch_closest_mean(V, beta), rows)
     C = _C_for(rows)
     if rows.device.type == "cuda":
         out = torch.empty(rows.d, dtype=rows.dtype, device=rows.device)
-        C.gpu_coordwise(rows.obj, _MODE["bulyan-tail"], f, beta, W.reshape(-1), t, 0, 1.0, out)
-        return _finish(out, rows)
+        return _finish(bulyan_tail_into(C, rows.obj, W, n, f, out), rows)
     if C is None:
         return ref.bulyan(rows.stacked(), f, m).to(rows.out_dtype)
-    return _finish(C.cpu_coordwise(rows.obj, _MODE["bulyan-tail"], f, beta, W.reshape(-1), t, 0, 1.0), rows)
+    return _finish(bulyan_tail_host(C, rows.obj, W, n, f), rows)
 
 
-def _coord(rows: Rows, mode: str, f: int = 0, beta: int = 0, seed: int = 0, p: float = 1.0) -> torch.Tensor:
-    if _large(rows) and mode in _LARGE_MODE:
+# --------------------------------------------------------------------------- #
+# The resolved coordinate-wise rule
+
+
+@dataclass(frozen=True, eq=False)
+class CoordRule:
+    """A coordinate-wise rule with its kernel arguments resolved for ``n`` rows (see :func:`resolve_coord`).
+    An argument the rule does not read is passed as the kernels' neutral value. Condense's seed is an
+    argument of each run (it changes every step), not of the rule."""
+
+    rule: str
+    n: int
+    mode: int                  # the mode code of gpu_coordwise / cpu_coordwise
+    large_mode: int | None     # that of gpu_large_coord; None: the rule has no large form
+    f: int                     # trimmed-mean: values cut at each end
+    beta: int                  # averaged-median: values averaged around the median
+    p: float                   # condense: probability of keeping the median
+    takes_seed: bool           # condense
+    kw: dict                   # the rule's keyword arguments for :func:`aggregate`, the seed aside
+
+    def into(self, C, rows, out: torch.Tensor, seed: int = 0) -> torch.Tensor:
+        """``out`` (fp32 or the rows' dtype) = the rule over device rows (n <= MAX_ROWS), one launch."""
+        C.gpu_coordwise(rows, self.mode, self.f, self.beta, None, 0, seed if self.takes_seed else 0, self.p, out)
+        return out
+
+    def large_into(self, X: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """``out`` = the rule over a GPU [n, d'] matrix of up to LARGE_ROWS rows (gar_large.hip)."""
+        _native.native().gpu_large_coord(X, self.large_mode, self.f, self.beta, out)
+        return out
+
+    def kwargs(self, seed: int = 0) -> dict:
+        """The keyword arguments with which ``aggregate(rule, ...)`` runs the rule (a seed among its own wins)."""
+        return {"seed": seed, **self.kw} if self.takes_seed else self.kw
+
+
+def resolve_coord(rule: str, n: int, f: int = 0, gar_kwargs: dict | None = None) -> CoordRule:
+    """The :class:`CoordRule` of ``rule`` over ``n`` rows: defaults applied, arguments validated (ValueError).
+    ``gar_kwargs``: the rule's own keyword arguments (``beta``, ``p``, ``seed``); others only travel in ``kw``."""
+    if rule not in _MODE or rule == "bulyan-tail":
+        raise ValueError(rule)
+    kw = dict(gar_kwargs or {})
+    if rule not in ("median", "average-nan"):
+        kw["f"] = f
+    beta = (kw.get("beta") or n - f) if rule == "averaged-median" else 0
+    if rule == "trimmed-mean" and not 0 <= 2 * f < n:
+        raise ValueError(f"trimmed-mean: expected 0 <= 2f < n, got n = {n}, f = {f}")
+    if rule == "averaged-median" and not 1 <= beta <= n:
+        raise ValueError(f"averaged-median: expected 1 <= beta <= n, got beta = {beta}, n = {n}")
+    condense = rule == "condense"
+    return CoordRule(rule, n, _MODE[rule], _LARGE_MODE.get(rule), f if rule == "trimmed-mean" else 0, beta,
+                     float(kw.get("p", 0.9)) if condense else 1.0, condense, kw)
+
+
+def _coord(rows: Rows, cr: CoordRule, seed: int = 0) -> torch.Tensor:
+    if _large(rows) and cr.large_mode is not None:
         X = _matrix(rows)
-        out = torch.empty(rows.d, dtype=X.dtype, device=X.device)
-        _native.native().gpu_large_coord(X, _LARGE_MODE[mode], f, beta, out)
-        return _finish(out, rows)
+        return _finish(cr.large_into(X, torch.empty(rows.d, dtype=X.dtype, device=X.device)), rows)
     if rows.n > MAX_ROWS:
-        return _finish(_torch_coord(rows.stacked().float(), mode, f, beta, seed, p), rows)
+        return _finish(_torch_coord(rows.stacked().float(), cr.rule, cr.f, cr.beta, seed, cr.p), rows)
     C = _C_for(rows)
-    code = _MODE[mode]
     if rows.device.type == "cuda":
-        out = torch.empty(rows.d, dtype=rows.dtype, device=rows.device)
-        C.gpu_coordwise(rows.obj, code, f, beta, None, 0, seed, p, out)
-        return _finish(out, rows)
+        return _finish(cr.into(C, rows.obj, torch.empty(rows.d, dtype=rows.dtype, device=rows.device), seed), rows)
     if C is None:
         X = rows.stacked()
-        r = {"median": lambda: ref.median(X), "trimmed-mean": lambda: ref.trimmed_mean(X, f),
-             "averaged-median": lambda: ref.averaged_median(X, beta), "average-nan": lambda: ref.average_nan(X),
-             "condense": lambda: ref.condense(X, p, seed)}[mode]()
+        r = {"median": lambda: ref.median(X), "trimmed-mean": lambda: ref.trimmed_mean(X, cr.f),
+             "averaged-median": lambda: ref.averaged_median(X, cr.beta), "average-nan": lambda: ref.average_nan(X),
+             "condense": lambda: ref.condense(X, cr.p, seed)}[cr.rule]()
         return r.to(rows.out_dtype)
-    return _finish(C.cpu_coordwise(rows.obj, code, f, beta, None, 0, seed, p), rows)
+    return _finish(C.cpu_coordwise(rows.obj, cr.mode, cr.f, cr.beta, None, 0, seed, cr.p), rows)
 
 
 def median(gradients, **_) -> torch.Tensor:
-    return _coord(prepare(gradients), "median")
+    rows = prepare(gradients)
+    return _coord(rows, resolve_coord("median", rows.n))
 
 
 def trimmed_mean(gradients, f: int, **_) -> torch.Tensor:
-    return _coord(prepare(gradients), "trimmed-mean", f=f)
+    rows = prepare(gradients)
+    return _coord(rows, resolve_coord("trimmed-mean", rows.n, f))
 
 
 def averaged_median(gradients, f: int = 0, beta: int | None = None, **_) -> torch.Tensor:
     rows = prepare(gradients)
-    beta = rows.n - f if beta is None else beta
-    return _coord(rows, "averaged-median", beta=beta)
+    return _coord(rows, resolve_coord("averaged-median", rows.n, f, {"beta": beta}))
 
 
 def average_nan(gradients, **_) -> torch.Tensor:
-    return _coord(prepare(gradients), "average-nan")
+    rows = prepare(gradients)
+    return _coord(rows, resolve_coord("average-nan", rows.n))
 
 
 def condense(gradients, p: float = 0.9, seed: int | None = None, **_) -> torch.Tensor:
     if seed is None:
         seed = int(torch.randint(0, 2**62, (1,)).item())
-    return _coord(prepare(gradients), "condense", seed=seed, p=p)
+    rows = prepare(gradients)
+    return _coord(rows, resolve_coord("condense", rows.n, gar_kwargs={"p": p}), seed)
 
 
 def brute_weights(gradients, f: int) -> torch.Tensor:
@@ -688,44 +747,54 @@ def brute_weights(gradients, f: int) -> torch.Tensor:
 
 def brute(gradients, f: int, **_) -> torch.Tensor:
     rows = prepare(gradients)
-    return _combine_rows(rows, brute_weights(rows, f))
+    return combine(rows, brute_weights(rows, f))
+
+
+def aksel_count(n: int, f: int, mode: str = "mid") -> int:
+    """The rows Aksel keeps: the closer half (``mode`` "mid"), else all but f."""
+    return (n + 1) // 2 if mode == "mid" else n - f
+
+
+def aksel_weights_from_distances(D: torch.Tensor, c: int) -> torch.Tensor:
+    """Aksel's weights ([..., n] fp32 on D's device) from the squared distances to the median ``D`` [..., n]:
+    1 / c on the c closest rows, ties by index, a non-finite distance counting as +inf."""
+    D = torch.where(torch.isfinite(D), D, torch.full_like(D, math.inf))
+    idx = torch.sort(D, dim=-1, stable=True).indices[..., :c]
+    return torch.zeros(D.shape, dtype=torch.float32, device=D.device).scatter_(-1, idx, 1.0 / c)
+
+
+def aksel_sqdist_slabs(C, ws: Workspace, median: CoordRule, rows, d: int) -> torch.Tensor:
+    """[grid, n] partial squared distances of the device rows (n <= MAX_ROWS, length d) to their coordinate-wise
+    median (``median``: the resolved rule): its launch, then gpu_sqdist. Additive over coordinate blocks."""
+    med = median.into(C, rows, ws.get("aksel_med", d))
+    grid = C.sqdist_grid(d)
+    slabs = ws.get("aksel_slabs", grid * median.n)
+    C.gpu_sqdist(rows, med, slabs)
+    return slabs.view(grid, median.n)
 
 
 def aksel_weights(gradients, f: int, mode: str = "mid") -> torch.Tensor:
     rows = prepare(gradients)
-    return _aksel_w(rows, f, mode)
-
-
-def _aksel_w(rows: Rows, f: int, mode: str) -> torch.Tensor:
-    c = (rows.n + 1) // 2 if mode == "mid" else rows.n - f
+    c = aksel_count(rows.n, f, mode)
     C = _C_for(rows)
     if rows.device.type == "cuda" and rows.n <= MAX_ROWS:
         ws = workspace(rows)
-        med = ws.get("aksel_med", rows.d)
-        C.gpu_coordwise(rows.obj, _MODE["median"], 0, 0, None, 0, 0, 1.0, med)
-        grid = C.sqdist_grid(rows.d)
-        slabs = ws.get("aksel_slabs", grid * rows.n)
-        C.gpu_sqdist(rows.obj, med, slabs)
         w = ws.get("weights", rows.n)
-        dists = ws.get("aksel_dists", rows.n)
-        C.gpu_aksel_select(slabs, rows.n, c, w, dists)
+        slabs = aksel_sqdist_slabs(C, ws, resolve_coord("median", rows.n), rows.obj, rows.d)
+        C.gpu_aksel_select(slabs.view(-1), rows.n, c, w, ws.get("aksel_dists", rows.n))
         return w
     if C is None or rows.n > MAX_ROWS:
         X = rows.stacked().double()
         med = _torch_coord(X, "median", 0, 0, 0, 1.0) if rows.n > MAX_ROWS else ref.median(X)
         dist = ((X - med.to(X.device)) ** 2).sum(1).cpu()
-        dist = torch.where(torch.isfinite(dist), dist, torch.full_like(dist, math.inf))
-        order = sorted(range(rows.n), key=lambda j: (float(dist[j]), j))
-        w = torch.zeros(rows.n, dtype=torch.float32)
-        w[order[:c]] = 1.0 / c
-        return w.to(rows.device)
+        return aksel_weights_from_distances(dist, c).to(rows.device)
     med = C.cpu_coordwise(rows.obj, _MODE["median"], 0, 0, None, 0, 0, 1.0)
     return C.cpu_aksel_weights(C.cpu_sqdist(rows.obj, med), c)
 
 
 def aksel(gradients, f: int, mode: str = "mid", **_) -> torch.Tensor:
     rows = prepare(gradients)
-    return _combine_rows(rows, _aksel_w(rows, f, mode))
+    return combine(rows, aksel_weights(rows, f, mode))
 
 
 # --------------------------------------------------------------------------- #

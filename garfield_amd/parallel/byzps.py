@@ -69,6 +69,9 @@ class ByzantinePSDataParallel(RobustDataParallel):
         self.M = torch.zeros((self.num_ps, self.ld), dtype=torch.float32, device=self.device)
         self._ps_gen = torch.Generator(device=self.device)
         self._ps_gen.manual_seed(cfg.seed + 31 * ctx.rank)
+        # the model aggregation as one coordinate-wise launch into the master vector, where the rule has one
+        self._mar = gar.resolve_coord(cfg.mar, cfg.num_ps, cfg.fps) \
+            if cfg.mar in COORD_RULES and cfg.mar not in ("bulyan", "condense") else None
 
     def _check_gar(self) -> None:
         from garfield_amd import aggregators
@@ -150,12 +153,10 @@ class ByzantinePSDataParallel(RobustDataParallel):
     def _write_mar(self, models: list) -> None:
         cfg = self.cfg
         out = self.flat.data[: self.d]
-        kw = {} if cfg.mar in ("average", "median", "average-nan") else {"f": cfg.fps}
-        if self.device.type == "cuda" and cfg.mar in COORD_RULES and cfg.mar not in ("bulyan", "condense"):
-            modes = gar._MODE
-            beta = len(models) - cfg.fps
-            self._C.gpu_coordwise(models, modes[cfg.mar], cfg.fps, beta, None, 0, 0, 1.0, out)
+        if self.device.type == "cuda" and self._mar is not None:
+            self._mar.into(self._C, models, out)
         else:
+            kw = {} if cfg.mar in ("average", "median", "average-nan") else {"f": cfg.fps}
             agg = gar.aggregate(cfg.mar, models, **kw)
             with torch.no_grad():
                 out.copy_(agg)

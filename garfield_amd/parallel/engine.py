@@ -37,6 +37,7 @@ import torch.nn as nn
 from garfield_amd import _native
 from garfield_amd.ops import agr_attack, gar, selection
 from garfield_amd.parallel.comm import DistContext, all_gather_rows, collectives_on
+from garfield_amd.parallel.update import LW_JOB, SgdUpdate, lw_device_tables, lw_job_ranges, lw_jobs  # noqa: F401
 from garfield_amd.runtime.attacks import AGR_ATTACKS, NEEDS_ESTIMATES, apply_attack
 from garfield_amd.utils.flat import FlatParams
 from garfield_amd.utils.profiling import PhaseTimer
@@ -61,19 +62,6 @@ LAYERWISE_RULES = set(selection.TABLE) | {"aksel"}   # per-layer != flat only fo
 # Layer-wise Krum as device operations (gar_layerwise.hip: one segmented Gram launch, a batched
 # selection, one segmented combine + SGD); "0" runs the per-segment loop (the reference form).
 LW_DEVICE = os.environ.get("GARFIELD_LW_DEVICE", "1") != "0"
-LW_JOB = 32768   # coordinates per job of the segmented kernels (a multiple of 64)
-
-
-def lw_job_ranges(x0: int, x1: int, origin: int = 0) -> list:
-    """[x0, x1) cut at the multiples of LW_JOB of the global coordinate (``origin``: the global
-    coordinate of local 0): every job boundary inside a segment is then a multiple of 64 whatever the
-    sharding, so the layer-wise tail's MFMA / exact split of the coordinates is sharding-invariant."""
-    out, a = [], x0
-    while a < x1:
-        e = min(((a + origin) // LW_JOB + 1) * LW_JOB - origin, x1)
-        out.append((a, e))
-        a = e
-    return out
 # fp32 (no autocast) worker batching on the GPU (the reference's precision): "1" (default) the grouped
 # NHWC executor on the fp32 kernels (conv_f32.hip, split-bf16 MFMA; bn_nhwc.hip in fp32), "0" the
 # per-worker path.
@@ -262,13 +250,15 @@ class RobustDataParallel:
         self.last_weights = None
         self.last_agr_gamma = {}   # adaptive attack kind -> the last step's γ (a one-element device tensor)
         self._C =_native.require_for(self.device) if self.device.type == "cuda" else None
-        self._one = torch.ones(1, dtype=torch.float32, device=self.device)
-        self._gagg = torch.zeros(self.ld, dtype=torch.float32, device=self.device) \
-            if cfg.gar in COORD_RULES else None
+        self._update = SgdUpdate(cfg, self._C, self.device)   # shared with the sharded aggregator
+        self._gagg = None   # the last fp32 aggregate of a rule that ends in one vector (_agg_vector)
+        if cfg.gar in COORD_RULES:
+            self._agg_vector()
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(cfg.seed + 7919 * self.rank)
         self._check_gar()
         self._sel = self._selection(self.n)   # resolved once: no argument handling per step
+        self._coord = self._coord_rule(self.n)
         self.timer = PhaseTimer(self.device, cfg.profile_phases)
         self._graph = None
         self._graph_failed = False
@@ -460,6 +450,25 @@ class RobustDataParallel:
             return selection.resolve(cfg.gar, n, cfg.f, cfg.m, cfg.pre_aggregation, cfg.gar_kwargs)
         return None
 
+    def _coord_rule(self, n: int):
+        """The configured rule resolved as a coordinate-wise rule over ``n`` rows (gar.resolve_coord); None
+        for any other rule (Bulyan included: a selection and its own tail)."""
+        cfg = self.cfg
+        if cfg.gar in COORD_RULES and cfg.gar != "bulyan":
+            return gar.resolve_coord(cfg.gar, n, cfg.f, cfg.gar_kwargs)
+        return None
+
+    def _target(self) -> tuple:
+        """What the unsharded update writes (parallel/update.py): the whole master vector, its momentum and
+        the working weights."""
+        return self.flat.data[: self.d], self.mom[: self.d], self._shadow
+
+    def _agg_vector(self) -> torch.Tensor:
+        """The fp32 scratch vector ([d], a view of ``_gagg``) of the rules that end in one aggregate vector."""
+        if self._gagg is None:
+            self._gagg = torch.zeros(self.ld, dtype=torch.float32, device=self.device)
+        return self._gagg[: self.d]
+
     def _check_gar(self) -> None:
         from garfield_amd import aggregators
 
@@ -540,36 +549,12 @@ class RobustDataParallel:
             return
         self._collude([self.G[s] for s in range(self.n)])
         rule = cfg.gar
-        kw = dict(cfg.gar_kwargs)
         if cfg.layerwise and rule in LAYERWISE_RULES:
             self._layerwise_update(rule, first)
-            self.step_count += 1
-            return
-        if self.device.type == "cuda" and self.n > gar.MAX_ROWS:
+        elif self.device.type == "cuda" and self.n > gar.MAX_ROWS:
             self._large_update(rule, first)
-        elif self.device.type == "cuda":
-            C = self._C
-            param, mom = self.flat.data[: self.d], self.mom[: self.d]
-            if rule in WEIGHTED_RULES:
-                w = self._weights()
-                self.last_weights = w
-                C.gpu_combine_sgd(self.G, w, param, mom, None, self._shadow, cfg.lr, cfg.momentum, cfg.dampening,
-                                  cfg.weight_decay, cfg.nesterov, first)
-            else:
-                g = self._gagg[: self.d]
-                self._coordinate(rule, kw, g)
-                C.gpu_combine_sgd(self._gagg.view(1, self.ld)[:, : self.d], self._one, param, mom, None, self._shadow,
-                                  cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
         else:
-            if cfg.pre_aggregation and rule in NNM_ENGINE_COORD_RULES:   # no weights: the rule over the set means
-                self.last_weights = None
-                g = gar.nnm_coord(self.G.float(), cfg.f, rule).float()
-            elif self._sel is not None and rule in WEIGHTED_RULES:   # kept for last_weights, then the rule's own combine
-                self.last_weights = w = self._weights(self.G.float())
-                g = gar.combine(self.G.float(), w).float()
-            else:
-                g = gar.aggregate(rule, self.G.float(), **self._rule_kwargs()).float()
-            self._sgd_cpu(g, first)
+            self._update_from_rows(self.G)
         self.step_count += 1
 
     def _large_update(self, rule: str, first: bool) -> None:
@@ -577,17 +562,13 @@ class RobustDataParallel:
         32 workers per GPU on 8 GPUs): the [n, d] set as one matrix on ``gar_large.hip``
         (compacted-weight combine, radix-select coordinate rules, split-K MFMA Gram for the
         selections), the aggregate rounded to the exchange dtype, then the fused update."""
-        cfg = self.cfg
         if rule in WEIGHTED_RULES:
-            w = self._weights()
-            self.last_weights = w
+            self.last_weights = w = self._weights()
             g = gar.combine(self.G, w)
         else:
             self.last_weights = None
             g = gar.aggregate(self._rule_name(), self.G, **self._rule_kwargs())
-        self._C.gpu_combine_sgd([g.contiguous()], self._one, self.flat.data[: self.d], self.mom[: self.d], None,
-                                self._shadow, cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov,
-                                first)
+        self._update.from_vector(g.contiguous(), self._target(), first)
 
     def _layerwise_update(self, rule: str, first: bool) -> None:
         """The GAR on every parameter tensor's slice of the [n, d] rows (each parameter is
@@ -598,15 +579,13 @@ class RobustDataParallel:
         launcher and the segmented Bulyan tail takes up to 64 rows. Otherwise a loop over the segments:
         weighted rules compute each segment's weights and combine it in fp32 (exactly the arithmetic of
         the device path), other rules aggregate the segment with the rule itself."""
-        cfg = self.cfg
         gkw = self._rule_kwargs()
         cuda = self.device.type == "cuda"
         if (cuda and LW_DEVICE and self._sel is not None and rule != "brute"
                 and self.n <= (64 if rule == "bulyan" else gar.MAX_ROWS)):
             self._layerwise_device(first)
             return
-        g = self._gagg if self._gagg is not None else torch.zeros(self.ld, dtype=torch.float32, device=self.device)
-        self._gagg = g
+        g = self._agg_vector()
         ws = []
         for off, numel in self._segments():
             seg = self.G[:, off:off + numel]
@@ -617,12 +596,7 @@ class RobustDataParallel:
             else:
                 g[off:off + numel].copy_(gar.aggregate(rule, seg if cuda else seg.float(), **gkw).float())
         self.last_weights = torch.stack(ws) if ws else None
-        if cuda:
-            self._C.gpu_combine_sgd(g.view(1, self.ld)[:, : self.d], self._one, self.flat.data[: self.d],
-                                    self.mom[: self.d], None, self._shadow, cfg.lr, cfg.momentum, cfg.dampening,
-                                    cfg.weight_decay, cfg.nesterov, first)
-        else:
-            self._sgd_cpu(g[: self.d], first)
+        self._update.from_vector(g, self._target(), first)
 
     def _segments(self) -> list:
         """(offset, numel) of every parameter segment, by offset."""
@@ -639,37 +613,22 @@ class RobustDataParallel:
         lw = getattr(self, "_lw", None)
         if lw is None:
             segs = self._segments()
-            jobs, seg_lo = [], [0]
-            for s, (off, numel) in enumerate(segs):
-                jobs.extend((a, e, s) for a, e in lw_job_ranges(off, off + numel))
-                seg_lo.append(len(jobs))
             offs = [o for o, _ in segs] + [segs[-1][0] + segs[-1][1]]
-            L, n = len(segs), self.n
-            np_ = C.gram_padded(n)
-            dev = self.device
+            L, dev = len(segs), self.device
             lw = self._lw = dict(
-                jobs=torch.tensor(jobs, dtype=torch.int64, device=dev),
-                seg_lo=torch.tensor(seg_lo, dtype=torch.int32, device=dev),
+                lw_device_tables(C, self.n, L, *lw_jobs(segs, 0, self.d), dev),
                 seg_off=torch.tensor(offs, dtype=torch.int64, device=dev),
-                slabs=torch.empty(len(jobs) * C.gram_slab_floats(n), dtype=torch.float32, device=dev),
-                gram=torch.empty(L * np_ * np_, dtype=torch.float32, device=dev),
-                ws=gar.Workspace(n, 0, dev), L=L)   # the selection's [L, n] buffers
+                ws=gar.Workspace(self.n, 0, dev), L=L)   # the selection's [L, n] buffers
         G = self.G[:, : self.d]
-        args = (cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
         C.gpu_lw_gram(G, lw["jobs"], lw["seg_lo"], lw["slabs"], lw["gram"])
         w = sel.on_device(C, lw["gram"], lw["ws"], lw["L"])
         if cfg.gar == "bulyan":
-            if self._gagg is None:
-                self._gagg = torch.zeros(self.ld, dtype=torch.float32, device=self.device)
-            g = self._gagg[: self.d]
-            C.gpu_lw_bulyan_tail(G, lw["jobs"], w.view(lw["L"], sel.t, sel.n), sel.t, sel.t - 2 * sel.f, g)
-            C.gpu_combine_sgd(g.view(1, -1), self._one, self.flat.data[: self.d], self.mom[: self.d], None,
-                              self._shadow, *args)
+            g = gar.bulyan_tail_into(C, G, w.view(lw["L"], sel.t, sel.n), sel.n, sel.f, self._agg_vector(), lw["jobs"])
+            self._update.from_vector(g, self._target(), first)
             self.last_weights = None
             return
         self.last_weights = w = w.view(lw["L"], sel.n)
-        C.gpu_lw_combine_sgd(G, lw["jobs"], lw["seg_off"], 0, w, self.flat.data[: self.d], self.mom[: self.d],
-                             self._shadow, *args)
+        self._update.segmented(G, lw["jobs"], lw["seg_off"], 0, w, self._target(), first)
 
     def _weights(self, G=None) -> torch.Tensor:
         """The configured rule's row weights (Bulyan: W [t, n]) over ``G`` (default: the [n, d] exchange rows)."""
@@ -688,35 +647,21 @@ class RobustDataParallel:
             return w
         return gar.aksel_weights(G, self.cfg.f, self.cfg.gar_kwargs.get("mode", "mid"))
 
-    def _coordinate(self, rule: str, kw: dict, out: torch.Tensor, G=None) -> None:
-        """Coordinate-wise rule (or Bulyan) over ``G`` (default: the [n, d] exchange rows;
-        else a list of rows) into the fp32 vector ``out``."""
-        C, f = self._C, self.cfg.f
-        modes = gar._MODE
-        G = self.G if G is None else G
-        n = len(G) if isinstance(G, (list, tuple)) else G.shape[0]
+    def _coordinate(self, out: torch.Tensor, G) -> torch.Tensor:
+        """The configured coordinate-wise rule (or Bulyan) over ``G`` (the [n, d] exchange rows or a list of
+        rows) into the fp32 vector ``out``."""
+        C, f, n = self._C, self.cfg.f, len(G)
         if self.cfg.pre_aggregation:   # Gram -> sets -> k_nnm_coord: the rule over the n set means, never stored
             rows = gar.prepare(G)
             ws = gar.workspace(rows)
-            gar.nnm_coord_into(C, ws, rows.obj, gar._gram_into(C, rows, ws), n, f, rule, out)
-        elif rule == "bulyan":
-            t = n - 2 * f - 2
-            W = self._weights(G)
-            C.gpu_coordwise(G, modes["bulyan-tail"], f, t - 2 * f, W.reshape(-1), t, 0, 1.0, out)
-        elif rule == "median":
-            C.gpu_coordwise(G, modes["median"], 0, 0, None, 0, 0, 1.0, out)
-        elif rule == "trimmed-mean":
-            C.gpu_coordwise(G, modes["trimmed-mean"], f, 0, None, 0, 0, 1.0, out)
-        elif rule == "averaged-median":
-            beta = kw.get("beta") or n - f
-            C.gpu_coordwise(G, modes["averaged-median"], f, beta, None, 0, 0, 1.0, out)
-        elif rule == "average-nan":
-            C.gpu_coordwise(G, modes["average-nan"], 0, 0, None, 0, 0, 1.0, out)
-        elif rule == "condense":
-            C.gpu_coordwise(G, modes["condense"], f, 0, None, 0, self.cfg.seed + self.step_count,
-                            float(kw.get("p", 0.9)), out)
-        else:
-            raise ValueError(rule)
+            gar.nnm_coord_into(C, ws, rows.obj, gar._gram_into(C, rows, ws), n, f, self.cfg.gar, out)
+            return out
+        if self.cfg.gar == "bulyan":
+            return gar.bulyan_tail_into(C, G, self._weights(G), n, f, out)
+        cr = self._coord if n == self.n else self._coord_rule(n)   # an explicit row list may be any subset
+        if cr is None:
+            raise ValueError(self.cfg.gar)
+        return cr.into(C, G, out, self.cfg.seed + self.step_count)
 
     def _rule_name(self) -> str:
         """The rule's name in gar.RULES: a coordinate-wise rule behind the mixing is its "nnm-" entry."""
@@ -724,64 +669,42 @@ class RobustDataParallel:
         return ("nnm-" + cfg.gar) if cfg.pre_aggregation and cfg.gar in NNM_ENGINE_COORD_RULES else cfg.gar
 
     def _rule_kwargs(self) -> dict:
+        """The keyword arguments with which the configured rule runs by name (gar.aggregate)."""
         cfg = self.cfg
+        if self._coord is not None:
+            return self._coord.kwargs(cfg.seed + self.step_count)
         kw = dict(cfg.gar_kwargs)
-        if cfg.gar not in ("average", "median", "average-nan"):
+        if cfg.gar != "average":
             kw["f"] = cfg.f
         if cfg.m is not None and self._sel is not None:   # the selections' m (of these, Bulyan runs by name)
             kw["m"] = cfg.m
-        if cfg.gar == "condense":
-            kw.setdefault("seed", cfg.seed + self.step_count)
         return kw
 
-    def _update_from_rows(self, rows: list) -> None:
-        """GAR over an explicit list of gradient rows (any subset of the slots, e.g. the
-        Byzantine-PS workers or a quorum) + the SGD update of this replica."""
+    def _update_from_rows(self, rows) -> None:
+        """GAR over the [n, d] exchange rows, or over an explicit list of gradient rows (any subset of the
+        slots, e.g. the Byzantine-PS workers or a quorum) + the SGD update of this replica."""
         cfg = self.cfg
         first = self.step_count == 0
-        param, mom = self.flat.data[: self.d], self.mom[: self.d]
         if self.device.type == "cuda":
-            C = self._C
             if cfg.gar in WEIGHTED_RULES:
                 self.last_weights = w = self._weights(rows)
-                C.gpu_combine_sgd(rows, w, param, mom, None, self._shadow, cfg.lr, cfg.momentum, cfg.dampening,
-                                  cfg.weight_decay, cfg.nesterov, first)
+                self._update.from_rows(rows, w, self._target(), first)
                 return
-            if self._gagg is None:
-                self._gagg = torch.zeros(self.ld, dtype=torch.float32, device=self.device)
-            g = self._gagg[: self.d]
+            g = self._agg_vector()
             if len(rows) <= gar.MAX_ROWS:   # fp32 aggregate, as the synchronous step's
-                self._coordinate(cfg.gar, dict(cfg.gar_kwargs), g, rows)
+                self._coordinate(g, rows)
             else:
                 g.copy_(gar.aggregate(self._rule_name(), rows, **self._rule_kwargs()))
-            C.gpu_combine_sgd([g], self._one, param, mom, None, self._shadow, cfg.lr, cfg.momentum, cfg.dampening,
-                              cfg.weight_decay, cfg.nesterov, first)
         else:
             # as a [rows, d] fp32 matrix: the aggregate keeps fp32 (a list of 16-bit rows
             # would round it to the rows' dtype), as the synchronous step's
-            X = torch.stack([r.float() for r in rows])
-            if cfg.gar in WEIGHTED_RULES and self._sel is not None:
+            X = rows.float() if isinstance(rows, torch.Tensor) else torch.stack([r.float() for r in rows])
+            if cfg.gar in WEIGHTED_RULES and self._sel is not None:   # kept for last_weights, then the rule's combine
                 self.last_weights = w = self._weights(X)
                 g = gar.combine(X, w).float()
             else:
                 g = gar.aggregate(self._rule_name(), X, **self._rule_kwargs()).float()
-            self._sgd_cpu(g, first)
-
-    def _sgd_cpu(self, g: torch.Tensor, first: bool) -> None:
-        cfg = self.cfg
-        p, buf = self.flat.data[: self.d], self.mom[: self.d]
-        with torch.no_grad():
-            if cfg.weight_decay:
-                g = g + cfg.weight_decay * p
-            if cfg.momentum:
-                if first:
-                    buf.copy_(g)
-                else:
-                    buf.mul_(cfg.momentum).add_(g, alpha=1 - cfg.dampening)
-                g = g + cfg.momentum * buf if cfg.nesterov else buf
-            p.add_(g, alpha=-cfg.lr)
-            if self._shadow is not None:
-                self._shadow[: self.d].copy_(p)
+        self._update.from_vector(g, self._target(), first)
 
     def _eager_step(self, batches) -> torch.Tensor:
         self._join()

@@ -57,9 +57,10 @@ import torch.distributed as dist
 from garfield_amd import _native
 from garfield_amd.ops import agr_attack, gar, selection
 from garfield_amd.parallel.comm import collectives_on, gloo_backend, world1_collectives
-from garfield_amd.parallel.engine import LAYERWISE_RULES, lw_job_ranges
+from garfield_amd.parallel.engine import LAYERWISE_RULES
 from garfield_amd.parallel.rccl import direct_backend
 from garfield_amd.parallel.signals import Handoff
+from garfield_amd.parallel.update import lw_device_tables, lw_jobs
 
 DISTANCE_RULES = set(selection.TABLE)   # decided from the summed partial Grams / distances
 SUPPORTED = DISTANCE_RULES | {"average", "aksel", "median", "trimmed-mean", "averaged-median", "average-nan",
@@ -74,7 +75,7 @@ def layerwise_device_ok(rule: str, n: int, f: int) -> bool:
     if n > gar.MAX_ROWS:
         return False
     if rule == "bulyan":
-        return n - 2 * f - 2 <= 64
+        return gar.bulyan_sizes(n, f)[0] <= 64
     if rule == "brute":
         return n <= 64
     return True   # krum, geomed, cclip, dnc (batched one-workgroup selections: n <= MAX_ROWS), aksel
@@ -171,7 +172,8 @@ class ShardedAggregator:
             b.rows = self._rows_of(b)
             if self._rccl is not None:
                 b.p2p = self._p2p_of(b)
-        self._one = torch.ones(1, dtype=torch.float32, device=dev)
+        self._update = e._update                       # the engine's SGD update, on this rank's shards
+        self._median = gar.resolve_coord("median", self.n)   # Aksel's centre
         self._avg = torch.full((self.n,), 1.0 / self.n, dtype=torch.float32, device=dev)
         self._ws = {}
         self._started = False
@@ -465,16 +467,15 @@ class ShardedAggregator:
         by the comm stream; or nothing to exchange)."""
         return self._comm_stream is not None
 
-    def _update_buckets(self, fn) -> None:
+    def _update_buckets(self, fn, staged: bool = True) -> None:
         """``fn(b)`` issues bucket b's update; buckets in update order (low coordinates first).
-        With the next forward staged (``self.staged``), the first bucket's update stays on the
+        With the next forward staged (``self.staged``, and ``staged``), the first bucket's update stays on the
         main stream and the others run on the comm stream (one device-side hand-off), each
         bucket followed by its weight all-gather and an event (``self._ready``) that the next
         forward's stage reading it waits on: the stem-to-layer2 forward runs while the
         layer3/layer4 updates and all-gathers are still in flight."""
-        order = self._update_order()
-        staged = self.staged and self.staging_ok()
-        for i, b in enumerate(order):
+        staged = staged and self.staged and self.staging_ok()
+        for i, b in enumerate(self._update_order()):
             if staged and i > 0:
                 if i == 1:
                     self._handoff.to_comm(torch.cuda.current_stream(self.e.device), self._comm_stream)
@@ -544,38 +545,36 @@ class ShardedAggregator:
         return ws
 
     def _param(self, b: _Bucket):
+        """Bucket b's update target (parallel/update.py): this rank's shard of it."""
         e = self.e
         mom = e.mom[b.moff:b.moff + b.S]
         shadow = e._shadow[b.own] if e._shadow is not None else None
         return e.flat.data[b.own], mom, shadow
 
+    def _aggregate_update(self, aggregate, first: bool, staged: bool = False) -> None:
+        """Every bucket, in update order: ``aggregate(b)`` returns the owned shard's aggregate as one vector
+        (usually written into b's scratch vector, ``_gagg``), b is updated from it and its weights are
+        all-gathered. ``staged``: the updates may run beside the next forward (``_update_buckets``)."""
+        self._update_buckets(lambda b: self._update.from_vector(aggregate(b), self._param(b), first), staged)
+
     def _gpu(self, cfg, first: bool) -> None:
         if self.n > gar.MAX_ROWS:
             return self._gpu_large(cfg, first)
         e, C = self.e, self.e._C
-        rule, f, kw = cfg.gar, cfg.f, dict(cfg.gar_kwargs)
-        n = self.n
-        args = (cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
-        modes = gar._MODE
+        rule, f, n = cfg.gar, cfg.f, self.n
         if rule in DISTANCE_RULES or rule == "aksel" or cfg.pre_aggregation:
             total = None
             slabs = []
             for b in self.buckets:   # partial statistics as the buckets land
                 self._wait(b)
-                rows = gar.prepare(b.rows)
                 ws = self._wsp(b)
                 if rule == "aksel":
-                    med = ws.get("aksel_med", b.S)
-                    C.gpu_coordwise(b.rows, modes["median"], 0, 0, None, 0, 0, 1.0, med)
-                    grid = C.sqdist_grid(b.S)
-                    sl = ws.get("aksel_slabs", grid * n)
-                    C.gpu_sqdist(b.rows, med, sl)
-                    slabs.append(sl.view(grid, n))
+                    slabs.append(gar.aksel_sqdist_slabs(C, ws, self._median, b.rows, b.S))
                 else:
-                    g = gar._gram_into(C, rows, ws)
+                    g = gar._gram_into(C, gar.prepare(b.rows), ws)
                     total = g.clone() if total is None else total.add_(g)
             if rule == "aksel":
-                c = (n + 1) // 2 if kw.get("mode", "mid") == "mid" else n - f
+                c = gar.aksel_count(n, f, cfg.gar_kwargs.get("mode", "mid"))
                 allslabs = self._concat_ranks(torch.cat(slabs))
                 w = self._ws_any().get("weights", n)
                 dists = self._ws_any().get("aksel_dists", n)
@@ -592,9 +591,8 @@ class ShardedAggregator:
                     def mixed(b):
                         g = self._gagg(b)
                         C.gpu_nnm_coord(b.rows, masks, n, f, rule, g)
-                        p, mom, sh = self._param(b)
-                        C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
-                    self._update_buckets(mixed)
+                        return g
+                    self._aggregate_update(mixed, first, True)
                     return
                 if n > e._sel.device_rows:
                     raise ValueError(f"{rule}: n must be <= {e._sel.device_rows} on the GPU")
@@ -602,49 +600,24 @@ class ShardedAggregator:
                 w = e._sel.on_device(C, total, self._ws_any())
             if rule != "bulyan":
                 e.last_weights = w
-
-                def combine(b):
-                    p, mom, sh = self._param(b)
-                    C.gpu_combine_sgd(b.rows, w, p, mom, None, sh, *args)
-                self._update_buckets(combine)
-                return
-            t = e._sel.t
-
-            def tail(b):
-                g = self._gagg(b)
-                C.gpu_coordwise(b.rows, modes["bulyan-tail"], f, t - 2 * f, w.reshape(-1), t, 0, 1.0, g)
-                p, mom, sh = self._param(b)
-                C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
-            self._update_buckets(tail)
+                self._update_buckets(lambda b: self._update.from_rows(b.rows, w, self._param(b), first))
+            else:
+                self._aggregate_update(lambda b: gar.bulyan_tail_into(C, b.rows, w, n, f, self._gagg(b)), first, True)
             return
         if rule == "average":
             e.last_weights = self._avg
+            for b in self.buckets:
+                self._wait(b)
+            self._update_buckets(lambda b: self._update.from_rows(b.rows, self._avg, self._param(b), first))
+            return
+        if e._coord is None:
+            raise ValueError(f"sharded aggregation does not support {rule!r}")
+        seed = cfg.seed + e.step_count
         for b in self.buckets:   # coordinate-wise aggregation as the buckets land
             self._wait(b)
-            if rule == "average":
-                continue
-            g = self._gagg(b)
-            if rule == "median":
-                C.gpu_coordwise(b.rows, modes["median"], 0, 0, None, 0, 0, 1.0, g)
-            elif rule == "trimmed-mean":
-                C.gpu_coordwise(b.rows, modes["trimmed-mean"], f, 0, None, 0, 0, 1.0, g)
-            elif rule == "averaged-median":
-                C.gpu_coordwise(b.rows, modes["averaged-median"], f, kw.get("beta") or n - f, None, 0, 0, 1.0, g)
-            elif rule == "average-nan":
-                C.gpu_coordwise(b.rows, modes["average-nan"], 0, 0, None, 0, 0, 1.0, g)
-            elif rule == "condense":
-                C.gpu_coordwise(b.rows, modes["condense"], f, 0, None, 0, cfg.seed + e.step_count + 7919 * b.lo,
-                                float(kw.get("p", 0.9)), g)
-            else:
-                raise ValueError(f"sharded aggregation does not support {rule!r}")
-
-        def update(b):
-            p, mom, sh = self._param(b)
-            if rule == "average":
-                C.gpu_combine_sgd(b.rows, self._avg, p, mom, None, sh, *args)
-            else:
-                C.gpu_combine_sgd([self._gagg(b)], self._one, p, mom, None, sh, *args)
-        self._update_buckets(update)
+            # condense draws its coin by the launch's own coordinate: without the offset every bucket repeats one mask
+            e._coord.into(C, b.rows, self._gagg(b), seed + 7919 * b.lo)
+        self._aggregate_update(self._gagg, first, True)
 
     def _matrix(self, b: _Bucket) -> torch.Tensor:
         """Bucket b's received shards as ONE [n, S] matrix (row pos[src] * k + j: the receive
@@ -660,9 +633,8 @@ class ShardedAggregator:
         compacted combine, radix-select coordinate rules). Selections are made in slot order (the
         partial Grams permuted once), then mapped back to the matrix's row order."""
         e, C = self.e, self.e._C
-        rule, f, kw = cfg.gar, cfg.f, dict(cfg.gar_kwargs)
+        rule, f = cfg.gar, cfg.f
         n, k, world = self.n, self.k, self.world
-        args = (cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
         perm = torch.tensor([self._pos[s % world] * k + s // world for s in range(n)], device=e.device)
         mats = {}
         for b in self.buckets:
@@ -679,40 +651,30 @@ class ShardedAggregator:
             # after the partial Grams are summed: the same selection on every rank, no host round trip
             ws = e._sel.from_gram(gs)
             if rule == "bulyan":
-                W = ws
-                Wm = torch.empty_like(W)
-                Wm[:, perm] = W
-                t, beta = n - 2 * f - 2, n - 4 * f - 2
+                Wm = torch.empty_like(ws)
+                Wm[:, perm] = ws
                 e.last_weights = None
-                for b in self._update_order():
-                    V = gar.large_wx(Wm, mats[b.lo])               # [t, S] fp32 on MFMA (bounded: one shard)
-                    g = self._gagg(b)
-                    C.gpu_large_coord(V, 2, 0, beta, g)
-                    p, mom, sh = self._param(b)
-                    C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
-                    self._gather_bucket(b)
+                # V = Wm·X: [t, S] fp32 on MFMA (bounded: one shard), then its radix-select tail
+                self._aggregate_update(
+                    lambda b: gar.bulyan_tail_large(gar.large_wx(Wm, mats[b.lo]), n, f, self._gagg(b)), first)
                 return
-        elif rule == "average":
-            ws = torch.full((n,), 1.0 / n, dtype=torch.float32, device=e.device)
         else:
-            ws = None
+            ws = torch.full((n,), 1.0 / n, dtype=torch.float32, device=e.device) if rule == "average" else None
         if ws is not None:
             e.last_weights = ws
             wm = torch.empty_like(ws)
             wm[perm] = ws
-        for b in self._update_order():
+        elif e._coord is None or e._coord.large_mode is None:
+            raise ValueError(f"sharded aggregation of more than {gar.MAX_ROWS} rows does not support {rule!r}")
+
+        def aggregate(b):   # in the rows' dtype, as the unsharded large step's
             X = mats[b.lo]
             out = torch.empty(b.S, dtype=X.dtype, device=e.device)
             if ws is not None:
                 C.gpu_large_combine(X, wm, out)
-            elif rule in gar._LARGE_MODE:
-                beta = kw.get("beta") or n - f
-                C.gpu_large_coord(X, gar._LARGE_MODE[rule], f, beta, out)
-            else:
-                raise ValueError(f"sharded aggregation of more than {gar.MAX_ROWS} rows does not support {rule!r}")
-            p, mom, sh = self._param(b)
-            C.gpu_combine_sgd([out], self._one, p, mom, None, sh, *args)
-            self._gather_bucket(b)
+                return out
+            return e._coord.large_into(X, out)
+        self._aggregate_update(aggregate, first)
 
     def _update_order(self) -> list:
         """Buckets by ascending coordinates: the next forward reads the low ones first."""
@@ -744,31 +706,18 @@ class ShardedAggregator:
         offs = [o for o, _ in segs] + [segs[-1][0] + segs[-1][1]]
         L = len(segs)
         plan = {"L": L, "offs": offs, "buckets": {}, "seg_id": {}}
+        cuda = e.device.type == "cuda"
         for b in self.buckets:
-            o0, o1 = b.own.start, b.own.stop
-            jobs, seg_lo = [], [0]
+            jobs, seg_lo = lw_jobs(segs, b.own.start, b.own.stop)
             sid = torch.full((b.S,), L, dtype=torch.int64)   # L: padding past the last segment
-            for si in range(L):
-                x0, x1 = max(offs[si], o0), min(offs[si + 1], o1)
-                if x1 > x0:
-                    sid[x0 - o0:x1 - o0] = si
-                jobs.extend((a - o0, e - o0, si) for a, e in lw_job_ranges(x0, x1))
-                seg_lo.append(len(jobs))
-            plan["buckets"][b.lo] = (jobs, seg_lo)
+            for a, z, s in jobs:
+                sid[a:z] = s
             plan["seg_id"][b.lo] = sid.to(e.device)
-        if e.device.type == "cuda":
-            C, dev, n = e._C, e.device, self.n
-            np_ = C.gram_padded(n)
-            plan["seg_off"] = torch.tensor(offs, dtype=torch.int64, device=dev)
-            for lo, (jobs, seg_lo) in list(plan["buckets"].items()):
-                J = max(len(jobs), 1)
-                plan["buckets"][lo] = dict(
-                    J=len(jobs),
-                    jobs=torch.tensor(jobs if jobs else [(0, 0, 0)], dtype=torch.int64, device=dev),
-                    seg_lo=torch.tensor(seg_lo, dtype=torch.int32, device=dev),
-                    slabs=torch.empty(J * C.gram_slab_floats(n), dtype=torch.float32, device=dev),
-                    gram=torch.empty(L * np_ * np_, dtype=torch.float32, device=dev))
-            plan["ws"] = gar.Workspace(n, 0, dev)   # the selection's [L, n] buffers
+            plan["buckets"][b.lo] = lw_device_tables(e._C, self.n, L, jobs, seg_lo, e.device) if cuda \
+                else (jobs, seg_lo)
+        if cuda:
+            plan["seg_off"] = torch.tensor(offs, dtype=torch.int64, device=e.device)
+            plan["ws"] = gar.Workspace(self.n, 0, e.device)   # the selection's [L, n] buffers
         self._lwp = plan
         return plan
 
@@ -787,7 +736,7 @@ class ShardedAggregator:
             S = rows[0].numel()
             if e.device.type == "cuda":
                 med = self._ws_any().get("lw_aksel_med", S)[:S]
-                e._C.gpu_coordwise(rows, gar._MODE["median"], 0, 0, None, 0, 0, 1.0, med)
+                self._median.into(e._C, rows, med)
             else:
                 med = gar.aggregate("median", torch.stack([r.float() for r in rows])).float()
             sid = plan["seg_id"][lo]
@@ -796,21 +745,17 @@ class ShardedAggregator:
                 X = torch.stack([r[a:z] for r in rows]).float()
                 D.index_add_(1, sid[a:z], ((X - med[a:z]) ** 2).double())
         D = self._sum_over_ranks(D[:, :L].t().contiguous())
-        D = torch.where(torch.isfinite(D), D, torch.full_like(D, math.inf))
-        c = (n + 1) // 2 if dict(cfg.gar_kwargs).get("mode", "mid") == "mid" else n - cfg.f
-        idx = torch.sort(D, dim=1, stable=True).indices[:, :c]
-        return torch.zeros((L, n), dtype=torch.float32, device=D.device).scatter_(1, idx, 1.0 / c)
+        return gar.aksel_weights_from_distances(D, gar.aksel_count(n, cfg.f, cfg.gar_kwargs.get("mode", "mid")))
 
     def _layerwise(self, cfg, first: bool) -> None:
         e, sel = self.e, self.e._sel   # sel: None for Aksel (distances to the median, not pairwise)
         rule = cfg.gar
         n, f = self.n, cfg.f
-        t = n - 2 * f - 2
+        t = gar.bulyan_sizes(n, f)[0]
         plan = self._lw_plan()
         L = plan["L"]
         if e.device.type == "cuda":
             C = e._C
-            args = (cfg.lr, cfg.momentum, cfg.dampening, cfg.weight_decay, cfg.nesterov, first)
             if rule == "aksel":
                 def landed():
                     for b in self.buckets:
@@ -834,23 +779,21 @@ class ShardedAggregator:
                 if rule == "bulyan":
                     W = w.view(L, t, n)
                     e.last_weights = None
-                    for b in self._update_order():
-                        bp = plan["buckets"][b.lo]
-                        g = self._gagg(b)
+
+                    def tail(b):
+                        bp, g = plan["buckets"][b.lo], self._gagg(b)
                         if bp["J"]:
-                            C.gpu_lw_bulyan_tail(b.rows, bp["jobs"][: bp["J"]], W, t, t - 2 * f, g)
-                        p, mom, sh = self._param(b)
-                        C.gpu_combine_sgd([g], self._one, p, mom, None, sh, *args)
-                        self._gather_bucket(b)
+                            gar.bulyan_tail_into(C, b.rows, W, n, f, g, bp["jobs"][: bp["J"]])
+                        return g
+                    self._aggregate_update(tail, first)
                     return
                 w = w.view(L, n)
             e.last_weights = w
             for b in self._update_order():
                 bp = plan["buckets"][b.lo]
                 if bp["J"]:
-                    p, mom, sh = self._param(b)
-                    C.gpu_lw_combine_sgd(b.rows, bp["jobs"][: bp["J"]], plan["seg_off"], b.own.start, w,
-                                         p, mom, sh, *args)
+                    self._update.segmented(b.rows, bp["jobs"][: bp["J"]], plan["seg_off"], b.own.start, w,
+                                           self._param(b), first)
                 self._gather_bucket(b)
             return
         # CPU (gloo): per-segment partial squared distances of the owned coordinates (fp64)
@@ -875,91 +818,52 @@ class ShardedAggregator:
                 Ds.fill_diagonal_(math.inf)
                 W[si] = sel.on_host(Cn, Ds)
         e.last_weights = None if rule == "bulyan" else W
-        for b in self._update_order():
+
+        def aggregate(b):
             X = Xs[b.lo]
             g = torch.zeros(b.S, dtype=torch.float32)
             for a, z, si in plan["buckets"][b.lo][0]:
                 if rule != "bulyan":
                     g[a:z] = (W[si][:, None] * X[:, a:z]).sum(0)
-                elif Cn is not None:
-                    g[a:z] = Cn.cpu_coordwise(X[:, a:z], gar._MODE["bulyan-tail"], f, t - 2 * f, W[si].reshape(-1), t,
-                                              0, 1.0).float()
                 else:
-                    g[a:z] = gar._torch_closest_mean(W[si] @ X[:, a:z], t - 2 * f).float()
-            self._sgd_cpu(b, g, first)
-            self._gather_bucket(b)
+                    g[a:z] = gar.bulyan_tail_host(Cn, X[:, a:z], W[si], n, f).float()
+            return g
+        self._aggregate_update(aggregate, first)
 
     # ------------------------------------------------------------------ #
     # CPU (gloo): the owned shards concatenated, the C++ / oracle building blocks
 
     def _cpu(self, cfg, first: bool) -> None:
-        e = self.e
         for b in self.buckets:
             self._wait(b)
-        order = sorted(self.buckets, key=lambda b: b.lo)
-        X = torch.cat([torch.stack([r.float() for r in b.rows]) for b in order], dim=1)   # [n, S] owned
+        X = torch.cat([torch.stack([r.float() for r in b.rows]) for b in self._update_order()], dim=1)   # [n, S] owned
         g = self._cpu_rule(cfg, X)
-        pos = 0
-        for b in order:
-            self._sgd_cpu(b, g[pos:pos + b.S], first)
-            self._gather_bucket(b)
-            pos += b.S
+        self._aggregate_update(lambda b: g[b.moff:b.moff + b.S], first)   # moff: b's offset among the owned shards
 
     def _cpu_rule(self, cfg, X: torch.Tensor) -> torch.Tensor:
         e = self.e
-        rule, f, kw = cfg.gar, cfg.f, dict(cfg.gar_kwargs)
+        rule, f = cfg.gar, cfg.f
         n = self.n
         if rule in DISTANCE_RULES or rule == "aksel" or cfg.pre_aggregation:
             C = _native.require_for(X.device)
             if rule == "aksel":
                 med = gar.aggregate("median", X)
-                part = ((X.double() - med.double()) ** 2).sum(1)
-                part = torch.where(torch.isfinite(part), part, torch.full_like(part, math.inf))
-                dist_ = self._sum_over_ranks(part)
-                c = (n + 1) // 2 if kw.get("mode", "mid") == "mid" else n - f
-                order = sorted(range(n), key=lambda j: (float(dist_[j]), j))
-                w = torch.zeros(n, dtype=torch.float32)
-                w[order[:c]] = 1.0 / c
-                e.last_weights = w
-                return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
-            D = self._sum_over_ranks(gar.pairwise_distances(X))
-            if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:   # the same sets on every rank, no weights
-                e.last_weights = None
-                return gar.nnm_coord_from_distances(C, X, D, f, rule)
-            w = e._sel.on_host(C, D)   # on the summed distances: the same selection on every rank
-            if rule == "bulyan":
-                t = n - 2 * f - 2
-                e.last_weights = None
-                if C is not None:
-                    return C.cpu_coordwise(X, gar._MODE["bulyan-tail"], f, t - 2 * f, w.reshape(-1), t, 0, 1.0)
-                return gar._torch_closest_mean(w @ X, t - 2 * f)
+                dist_ = self._sum_over_ranks(((X.double() - med.double()) ** 2).sum(1))
+                w = gar.aksel_weights_from_distances(dist_, gar.aksel_count(n, f, cfg.gar_kwargs.get("mode", "mid")))
+            else:
+                D = self._sum_over_ranks(gar.pairwise_distances(X))
+                if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:   # the same sets on every rank, no weights
+                    e.last_weights = None
+                    return gar.nnm_coord_from_distances(C, X, D, f, rule)
+                w = e._sel.on_host(C, D)   # on the summed distances: the same selection on every rank
+                if rule == "bulyan":
+                    e.last_weights = None
+                    return gar.bulyan_tail_host(C, X, w, n, f)
             e.last_weights = w
             return C.cpu_combine(X, w) if C is not None else (w[:, None] * X).sum(0)
         if rule == "average":
             return gar.aggregate("average", X).float()
-        gkw = dict(kw)
-        if rule not in ("median", "average-nan"):
-            gkw["f"] = f
-        if rule == "condense":
-            gkw.setdefault("seed", cfg.seed + e.step_count)
-        return gar.aggregate(rule, X, **gkw).float()
-
-    def _sgd_cpu(self, b: _Bucket, g: torch.Tensor, first: bool) -> None:
-        cfg = self.e.cfg
-        p, buf, _ = self._param(b)
-        with torch.no_grad():
-            if cfg.weight_decay:
-                g = g + cfg.weight_decay * p
-            if cfg.momentum:
-                if first:
-                    buf.copy_(g)
-                else:
-                    buf.mul_(cfg.momentum).add_(g, alpha=1 - cfg.dampening)
-                g = g + cfg.momentum * buf if cfg.nesterov else buf
-            p.add_(g, alpha=-cfg.lr)
-            sh = self.e._shadow
-            if sh is not None:
-                sh[b.own].copy_(p)
+        return gar.aggregate(rule, X, **e._coord.kwargs(cfg.seed + e.step_count)).float()
 
     # ------------------------------------------------------------------ #
     # optimizer state in the reference layout (checkpoints)

@@ -7,8 +7,9 @@ import pytest
 import torch
 
 import _layerwise_common as lw
-from garfield_amd.parallel.engine import LW_JOB, lw_job_ranges
+from garfield_amd.parallel.engine import LW_JOB
 from garfield_amd.parallel.sharded import ShardedAggregator
+from garfield_amd.parallel.update import lw_jobs
 
 
 def fp32_exact(t: torch.Tensor) -> bool:
@@ -73,8 +74,10 @@ def test_arbitrary_cut_has_the_named_edges():
 
 
 def test_jobs_are_the_engines_rules():
-    """The helper's tables against ShardedAggregator._lw_plan itself (run on a stub engine) and against
-    _layerwise_device's loop."""
+    """The helper's tables against the engines' one builder (parallel/update.py): called as _layerwise_device
+    calls it (the whole range) and as ShardedAggregator._lw_plan does (each owned range), and that plan
+    itself, run on a stub engine."""
+    segs = list(zip(lw.OFFS[:-1], lw.LENS))
     flat = SimpleNamespace(offsets=list(lw.OFFS[:-1]), numels=list(lw.LENS))
     for cut in (lw.whole_cut(), lw.shard_cuts()):
         buckets = [SimpleNamespace(lo=i, own=range(o0, o1), S=o1 - o0) for i, (o0, o1, _, _) in enumerate(cut)]
@@ -82,14 +85,14 @@ def test_jobs_are_the_engines_rules():
         plan = ShardedAggregator._lw_plan(stub)
         assert plan["L"] == lw.L and plan["offs"] == list(lw.OFFS)
         for i, (o0, o1, jobs, seg_lo) in enumerate(cut):
+            assert lw_jobs(segs, o0, o1) == (jobs, seg_lo)
             assert plan["buckets"][i] == (jobs, seg_lo)
             sid = plan["seg_id"][i]
             assert all(int(sid[a]) == s and int(sid[e - 1]) == s for a, e, s in jobs)
-    jobs, seg_lo = [], [0]
-    for s, (off, numel) in enumerate(zip(lw.OFFS, lw.LENS)):                 # _layerwise_device
-        jobs.extend((a, e, s) for a, e in lw_job_ranges(off, off + numel))
-        seg_lo.append(len(jobs))
-    assert (jobs, seg_lo) == lw.whole_cut()[0][2:]
+    assert lw_jobs(segs, 0, lw.D) == lw.whole_cut()[0][2:]                   # _layerwise_device
+    # a range that is not at local 0: the same jobs, shifted
+    o0, o1, jobs, seg_lo = lw.shard_cuts()[2]
+    assert lw_jobs(segs, o0, o1, 5) == ([(a + 5, e + 5, s) for a, e, s in jobs], seg_lo)
 
 
 # ---------------------------------------------------------------------------------------------

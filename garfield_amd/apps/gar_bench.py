@@ -24,13 +24,17 @@ from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
          "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average", "cclip", "cclip-krum", "nnm-cclip",
-         "nnm-trimmed-mean", "nnm-median", "dnc"]
+         "nnm-trimmed-mean", "nnm-median", "dnc",
+         "arc-krum", "arc-geomed", "arc-cclip", "arc-dnc", "arc-average", "arc-nnm-krum", "arc-nnm-geomed",
+         "arc-nnm-cclip", "arc-nnm-average", "arc-trimmed-mean", "arc-median", "arc-nnm-trimmed-mean", "arc-nnm-median"]
 # "cclip-krum": centered clipping from the Multi-Krum start (start="krum"), Krum's f
 
 
 def default_f(rule: str, n: int) -> int | None:
+    if rule.startswith("arc-"):   # adaptive robust clipping in front: the f of what it stands in front of
+        rule = rule[4:] if rule.startswith("arc-nnm-") else "nnm-" + rule[4:]
     if rule.startswith("nnm-"):   # the f of the plain rule (average: as geomed, median: as the trimmed mean:
-        # the plain median takes no f, the mixing needs one), so the pair is comparable
+        # the plain median takes no f, the mixing and the clipping need one), so the pair is comparable
         rule = {"nnm-average": "geomed", "nnm-median": "trimmed-mean"}.get(rule, rule[4:])
     if rule == "cclip-krum":
         rule = "krum"
@@ -131,7 +135,7 @@ def main(argv=None):
             for rule in a.rules:
                 f = default_f(rule, n)
                 if rule in ("krum", "nnm-krum", "cclip-krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense",
-                            "nnm-trimmed-mean", "nnm-median") and f is None:
+                            "nnm-trimmed-mean", "nnm-median") + tuple(r for r in RULES if r.startswith("arc-")) and f is None:
                     continue
                 if rule == "brute" and n > 20:
                     continue

@@ -318,6 +318,27 @@ void g_nnm_coord(const RowSet& rs, const at::Tensor& masks, int n, int f, const 
                            dtype_code(out), stream_of(rs.device));
 }
 
+// clip_rows [n + 1] int32 and scales [n] fp32 of gpu_arc_scale on the rows' device
+void check_arc_lists(const char* who, const at::Tensor& scales, const at::Tensor& clip_rows, int n, int batch,
+                     const at::Device& dev) {
+  TORCH_CHECK(scales.device() == dev && clip_rows.device() == dev && dev.is_cuda(), who, ": GPU tensors on one device expected");
+  TORCH_CHECK(clip_rows.scalar_type() == at::kInt && clip_rows.is_contiguous(), who, ": clip_rows must be contiguous int32");
+  TORCH_CHECK(scales.numel() >= static_cast<int64_t>(batch) * n && clip_rows.numel() >= static_cast<int64_t>(batch) * (n + 1),
+              who, ": buffers too small for the batch");
+  (void)fptr(scales);
+}
+
+void g_arc_apply(const RowSet& rs, const at::Tensor& scales, const at::Tensor& clip_rows, int f, int64_t lo, int64_t hi) {
+  TORCH_CHECK(rs.device.is_cuda() && rs.dt != garfield::kF64, "gpu_arc_apply: fp32, bf16 or fp16 GPU rows");
+  TORCH_CHECK(f >= 0 && f < rs.n, "gpu_arc_apply: 0 <= f < n");
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= rs.d, "gpu_arc_apply: 0 <= lo <= hi <= row length");
+  TORCH_CHECK(hi < (int64_t{1} << 31), "gpu_arc_apply: hi < 2^31");
+  check_arc_lists("gpu_arc_apply", scales, clip_rows, rs.n, 1, rs.device);
+  c10::hip::HIPGuard guard(rs.device.index());
+  garfield::gpu::arc_apply(rs.table, rs.n, garfield::gpu::arc_count(rs.n, f), lo, hi, rs.dt, clip_rows.data_ptr<int>(),
+                           fptr(scales), stream_of(rs.device));
+}
+
 void g_sqdist(const RowSet& rs, const at::Tensor& center, const at::Tensor& slabs) {
   check_gpu(rs);
   c10::hip::HIPGuard guard(rs.device.index());
@@ -2170,6 +2191,51 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            "NNM before a coordinate-wise rule: out[x] = mode ('trimmed-mean' with f / 'median') over the n means of the "
            "rows in each set of masks [n, 2], per coordinate; the mixed rows are never stored. args (rows, masks, n, f, "
            "mode, out); out fp32 or the rows' dtype");
+  m.def("arc_count", [](int n, int f) {
+    TORCH_CHECK(n >= 1 && f >= 0 && f < n, "arc_count: n >= 1 and 0 <= f < n");
+    return garfield::gpu::arc_count(n, f);
+  }, py::arg("n"), py::arg("f"), "Rows adaptive robust clipping may clip: 2 f (n - f) / n");
+  m.def("gpu_arc_scale", [](const at::Tensor& gram, int n, int f, const at::Tensor& scales, const at::Tensor& clip_rows,
+                            const c10::optional<at::Tensor>& gram_out, int batch) {
+    const int np = check_select("gpu_arc_scale", gram, n, batch, {{scales, n}, {clip_rows, n + 1}});
+    TORCH_CHECK(f >= 0 && f < n, "gpu_arc_scale: 0 <= f < n");
+    check_arc_lists("gpu_arc_scale", scales, clip_rows, n, batch, gram.device());
+    float* out = nullptr;
+    if (gram_out.has_value()) {
+      TORCH_CHECK(gram_out->device() == gram.device() && gram_out->numel() >= static_cast<int64_t>(batch) * np * np,
+                  "gpu_arc_scale: gram_out must be a GPU tensor of the Gram's size");
+      out = fptr(*gram_out);
+    }
+    c10::hip::HIPGuard guard(gram.device().index());
+    garfield::gpu::arc_scale(fptr(gram), np, n, f, fptr(scales), clip_rows.data_ptr<int>(), out, stream_of(gram.device()),
+                             batch);
+  }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("scales"), py::arg("clip_rows"), py::arg("gram_out") = py::none(),
+     py::arg("batch") = 1,
+     "Adaptive robust clipping on the Gram's diagonal: scales [n] fp32 (sqrt(C2 / s_i) on the rows above the "
+     "(k + 1)-th largest squared norm C2, k = 2 f (n - f) / n, else 1), clip_rows [n + 1] int32 (count, the clipped rows "
+     "ascending, -1) and, when given, gram_out [np, np] = (c_i c_j) G_ij; batch > 1: gram [batch, np, np] -> [batch, ...]");
+  m.def("gpu_arc_fold", [](const at::Tensor& a, const at::Tensor& scales, int n, const at::Tensor& w, int batch) {
+    TORCH_CHECK(n >= 1 && n <= garfield::kMaxRows, "gpu_arc_fold: 1 <= n <= ", garfield::kMaxRows);
+    TORCH_CHECK(batch >= 1, "gpu_arc_fold: batch must be >= 1");
+    TORCH_CHECK(a.is_cuda() && w.device() == a.device() && scales.device() == a.device(),
+                "gpu_arc_fold: GPU tensors on one device expected");
+    TORCH_CHECK(a.numel() >= static_cast<int64_t>(batch) * n && w.numel() >= static_cast<int64_t>(batch) * n &&
+                    scales.numel() >= static_cast<int64_t>(batch) * n,
+                "gpu_arc_fold: buffers too small for the batch");
+    c10::hip::HIPGuard guard(a.device().index());
+    garfield::gpu::arc_fold(fptr(a), fptr(scales), n, fptr(w), stream_of(a.device()), batch);
+  }, py::arg("a"), py::arg("scales"), py::arg("n"), py::arg("w"), py::arg("batch") = 1,
+     "Fold weights a [n] over the clipped rows back onto the original rows: w_j = scales_j * a_j");
+  def_rows(m, "gpu_arc_apply",
+           [](const at::Tensor& G, const at::Tensor& scales, const at::Tensor& clip_rows, int f, int64_t lo, int64_t hi) {
+             TORCH_CHECK(G.dim() == 2 && (G.size(0) <= 1 || G.stride(0) >= G.size(1)),
+                         "gpu_arc_apply: the rows of a matrix must not overlap (row stride >= row length)");
+             g_arc_apply(rows_from_2d(G, false), scales, clip_rows, f, lo, hi);
+           },
+           [](const std::vector<at::Tensor>& L, const at::Tensor& scales, const at::Tensor& clip_rows, int f, int64_t lo,
+              int64_t hi) { g_arc_apply(rows_from_list(L, false), scales, clip_rows, f, lo, hi); },
+           "Clip in place: every row listed in clip_rows <- cast(scales[row] * row) on the coordinates [lo, hi); rows "
+           "of any stride and alignment; args (rows, scales, clip_rows, f, lo, hi), the grid sized by k = 2 f (n - f) / n");
   def_rows(m, "gpu_lw_gram",
            [](const at::Tensor& G, const at::Tensor& jobs, const at::Tensor& seg_lo, const at::Tensor& slabs,
               const at::Tensor& gram) { g_lw_gram(rows_from_2d(G, true), jobs, seg_lo, slabs, gram); },

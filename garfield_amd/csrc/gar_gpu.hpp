@@ -70,6 +70,21 @@ void nnm_sets(const float* gram, int np, int n, int f, unsigned long long* masks
 void nnm_coord(const RowTable& rows, int n, int64_t d, int dt, int mode, int f, const unsigned long long* masks,
                void* out, int out_dt, hipStream_t stream);
 
+// Adaptive robust clipping (gar_arc.hip), n <= kMaxRows, 0 <= f < n, k = arc_count(n, f) = 2 f (n - f) / n.
+// arc_scale: from the Gram's diagonal s, C² = the (k + 1)-th largest s by (s descending, index ascending, a
+// non-finite s as +inf); scales[n] = sqrt(C² / s_i) where s_i and C² are finite and s_i > C², else 1;
+// clip_rows[n + 1] = the number of rows with a scale != 1 (<= k), their indices ascending, then -1;
+// gram_out [np][np] (nullptr: not written; may be gram) = (c_i c_j) G_ij, on which the selections run
+// unchanged. arc_fold: w[n] = scales[n] * a[n] (w may be a). batch as krum_select.
+// arc_apply: rows listed in clip_rows <- cast(scale * row) on the coordinates [lo, hi), in place; k is the
+// host's bound on the count (no launch when 0); rows need no alignment; hi < 2^31.
+int arc_count(int n, int f);
+void arc_scale(const float* gram, int np, int n, int f, float* scales, int* clip_rows, float* gram_out,
+               hipStream_t stream, int batch = 1);
+void arc_fold(const float* a, const float* scales, int n, float* w, hipStream_t stream, int batch = 1);
+void arc_apply(const RowTable& rows, int n, int k, int64_t lo, int64_t hi, int dt, const int* clip_rows, const float* scales,
+               hipStream_t stream);
+
 // W[t][n]: row k = uniform weights of the (m-k) best-scoring gradients at step k
 // batch > 1: gram [batch][np][np] -> W [batch][t][n]
 void bulyan_select(const float* gram, int np, int n, int f, int m, int t, float* W,

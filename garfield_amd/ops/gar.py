@@ -14,6 +14,9 @@ current stream, nothing copied to the host:
   n x n distances -> combine;
 * Nearest-neighbour mixing before Krum / geometric median / centered clipping / average: Gram -> one-workgroup mix
   (neighbour sets + the mixed rows' pseudo-Gram) -> the rule's selection -> un-mix -> combine;
+* Adaptive robust clipping before any of those (and before the mixing): Gram -> one-workgroup scales + the clipped
+  rows' Gram -> (mix ->) the rule's selection -> (un-mix ->) fold the scales into the weights -> combine; before the
+  coordinate-wise trimmed mean / median: the clipped rows rewritten on a private copy -> the rule;
 * Bulyan: Gram -> on-device selection loop -> W[t, n] -> fused W·G averaged-median;
 * Brute: Gram -> device-wide subset search (atomicMin on (diameter, rank)) -> combine;
 * Median / Trimmed-Mean / Averaged-Median / Average-NaN / Condense: register
@@ -44,8 +47,9 @@ import torch
 from garfield_amd import _native
 from garfield_amd.ops import reference as ref
 # the distance-based selections live in ops/selection.py; their Gram forms keep their names here
-from garfield_amd.ops.selection import (BRUTE_MAX_SUBSETS, CCLIP_STARTS, MAX_ROWS, NNM_RULES,  # noqa: F401
-                                        Selection, cclip_weights_from_gram, distances_from_gram,
+from garfield_amd.ops.selection import (ARC_RULES, BRUTE_MAX_SUBSETS, CCLIP_STARTS, MAX_ROWS, NNM_RULES,  # noqa: F401
+                                        Selection, arc_count, arc_distances, arc_gram, arc_scales_from_sqnorms,
+                                        cclip_weights_from_gram, distances_from_gram,
                                         dnc_weights_from_gram, geomed_weights_from_gram, krum_weights_from_gram,
                                         large_bulyan_weights as _large_bulyan_weights, large_select,
                                         nan_inf as _nan_inf, nnm_from_gram, resolve)
@@ -330,7 +334,17 @@ def selection_weights(gradients, sel: Selection) -> torch.Tensor:
         D = pairwise_distances(rows.obj)
     else:
         D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
+    if sel.clips:   # distances lose the norms ARC decides from: they travel beside D
+        return sel.on_host(C, D, _sqnorms(rows)).to(rows.device)
     return sel.on_host(C, D).to(rows.device)
+
+
+def _sqnorms(rows: Rows) -> torch.Tensor:
+    """The rows' squared norms [n] (fp64, CPU): the Gram's diagonal on the GPU, fp64 sums on the CPU."""
+    if rows.device.type == "cuda":
+        return torch.diagonal(gram(rows)).double().cpu()
+    X = rows.stacked().double()
+    return (X * X).sum(1)
 
 
 def krum_weights(gradients, f: int, m: int | None = None, pre: str | None = None) -> torch.Tensor:
@@ -366,12 +380,13 @@ def geomed(gradients, f: int = 0, iters: int = 32, nu: float = 1e-6, **_) -> tor
 # kv lowest scores) for the combine kernels.
 
 
-def dnc_weights(gradients, f: int, m: int | None = None, iters: int = 16) -> torch.Tensor:
+def dnc_weights(gradients, f: int, m: int | None = None, iters: int = 16, pre: str | None = None) -> torch.Tensor:
     """Selection weights of DnC spectral filtering ([n] fp32 on the gradients' device): 1 / m on the
     ``m`` (default ``n - f``) rows of lowest outlier score, the squared projection on the top principal
-    direction of the centred rows, from ``iters`` power rounds on the pairwise distances alone."""
+    direction of the centred rows, from ``iters`` power rounds on the pairwise distances alone. ``pre="arc"``:
+    the row weights of DnC over the adaptively clipped rows (:func:`arc_weights`)."""
     rows = prepare(gradients)
-    return selection_weights(rows, resolve("dnc", rows.n, f, m, None, {"iters": iters}))
+    return selection_weights(rows, resolve("dnc", rows.n, f, m, pre, {"iters": iters}))
 
 
 def dnc(gradients, f: int = 0, m: int | None = None, iters: int = 16, **_) -> torch.Tensor:
@@ -576,6 +591,127 @@ def nnm_coord(gradients, f: int, rule: str = "trimmed-mean") -> torch.Tensor:
         return ref.nnm_coord(rows.stacked(), f, rule).to(rows.out_dtype)
     _, masks = C.cpu_nnm_mix(C.cpu_pairwise(rows.obj), f)
     return _finish(C.cpu_mixed_coordwise(rows.obj, masks, n - f, rule, f), rows)   # rows.obj may be a list
+
+
+# Adaptive robust clipping (ARC; docs/GAR_SEMANTICS.md): the k = 2f(n - f) // n rows of largest norm are
+# scaled down to the (k + 1)-th largest norm before anything else runs. The decision needs the Gram's diagonal
+# alone and clipping is linear per row: for the weighted rules the scales fold into the Gram and into the
+# weights (no pass over the d-length rows); the coordinate-wise rules get the few clipped rows rewritten.
+
+ARC_COORD_RULES = NNM_COORD_RULES
+
+
+def _arc_pre(nnm: bool) -> str:
+    return "arc+nnm" if nnm else "arc"
+
+
+def _arc_args(n: int, f: int) -> None:
+    if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < n:
+        raise ValueError(f"arc: expected 0 <= f < n, got f = {f!r}, n = {n}")
+
+
+def arc_scales(gradients, f: int) -> torch.Tensor:
+    """The scales alone ([n] fp32 on the gradients' device): sqrt(C² / ||g_i||²) on the rows whose norm is
+    above the (k + 1)-th largest, 1 elsewhere. GPU, n <= MAX_ROWS: Gram -> k_arc_scale; else vectorised
+    on the Gram's diagonal (GPU) or on fp64 squared norms (CPU). Any 0 <= f < n."""
+    rows = prepare(gradients)
+    _arc_args(rows.n, f)
+    if rows.device.type != "cuda":
+        return arc_scales_from_sqnorms(_sqnorms(rows), f)
+    if rows.n > MAX_ROWS:
+        return arc_scales_from_sqnorms(torch.diagonal(_large_gram(rows)), f)
+    C = _C_for(rows)
+    ws = workspace(rows)
+    scales = torch.empty(rows.n, dtype=torch.float32, device=rows.device)
+    C.gpu_arc_scale(_gram_into(C, rows, ws), rows.n, f, scales, ws.get("arc_clip_rows", rows.n + 1, torch.int32))
+    return scales
+
+
+def arc_weights(gradients, f: int, rule: str = "krum", nnm: bool = False, **kw) -> torch.Tensor:
+    """Weights over the ORIGINAL rows ([n] fp32 on the gradients' device) of ``rule`` (krum: ``m``; geomed:
+    ``iters``, ``nu``; cclip: ``tau``, ``iters``, ``start`` "mean" / "krum", ``m``; dnc: ``m``, ``iters``;
+    average) applied to the adaptively clipped rows; ``nnm``: to those rows mixed over their n - f nearest
+    (not dnc). The weights sum to at most 1: a clipped row counts with its scale."""
+    rows = prepare(gradients)
+    return selection_weights(rows, resolve(rule, rows.n, f, kw.pop("m", None), _arc_pre(nnm), kw))
+
+
+def arc(gradients, f: int, rule: str = "krum", nnm: bool = False, **kw) -> torch.Tensor:
+    """``rule`` after adaptive robust clipping (and mixing, with ``nnm``): Σ_j w_j g_j with the weights of
+    :func:`arc_weights`; nothing is rounded to the gradients' dtype in between."""
+    rows = prepare(gradients)
+    return combine(rows, arc_weights(rows, f, rule, nnm, **kw))
+
+
+def arc_apply_into(C, ws: Workspace, G, g: torch.Tensor, n: int, f: int, lo: int, hi: int,
+                   gram_out: torch.Tensor | None = None) -> torch.Tensor:
+    """Clip the device rows ``G`` (a list or an [n, ld] matrix, n <= MAX_ROWS) in place on the coordinates
+    [lo, hi) from their device Gram ``g``: k_arc_scale, then k_arc_apply on the clipped rows only. Returns the
+    scales; ``gram_out``: the clipped rows' Gram as well. Every buffer comes from ``ws`` (capture-safe)."""
+    scales = ws.get("arc_scales", n)
+    clip_rows = ws.get("arc_clip_rows", n + 1, torch.int32)
+    C.gpu_arc_scale(g, n, f, scales, clip_rows, gram_out)
+    C.gpu_arc_apply(G, scales, clip_rows, f, lo, hi)
+    return scales
+
+
+def _clipped_copy(rows: Rows, c: torch.Tensor) -> torch.Tensor:
+    """A private [n, d] copy of the rows with the rows of scale != 1 as cast(c · float(x)) (torch)."""
+    X = rows.stacked().clone() if isinstance(rows.obj, torch.Tensor) else rows.stacked()
+    c = c.to(X.device)
+    hit = (c != 1).nonzero().flatten()
+    if hit.numel():
+        wide = torch.float64 if X.dtype == torch.float64 else torch.float32
+        X[hit] = (c[hit].to(wide)[:, None] * X[hit].to(wide)).to(X.dtype)
+    return X
+
+
+def arc_coord(gradients, f: int, rule: str = "trimmed-mean", nnm: bool = False) -> torch.Tensor:
+    """``rule`` ("trimmed-mean" with the same ``f``, or "median") over the adaptively clipped rows, in the
+    gradients' dtype; ``nnm``: over those rows mixed over their n - f nearest (the sets from the clipped
+    rows' Gram). The clipped rows are written as cast(c · float(x)) on a private copy: the inputs are never
+    modified. GPU, n <= MAX_ROWS: Gram -> k_arc_scale -> k_arc_apply on the copy -> the plain rule (or
+    k_nnm_coord); elsewhere the copy is clipped with torch."""
+    rows = prepare(gradients)
+    n = rows.n
+    _arc_args(n, f)
+    if nnm:
+        _nnm_coord_args(n, f, rule)
+    elif rule not in ARC_COORD_RULES:
+        raise ValueError(f"arc: unsupported coordinate-wise rule {rule!r}; available: {ARC_COORD_RULES}")
+    plain = resolve_coord(rule, n, f)   # the rule's own requirement (trimmed-mean: 2f < n)
+    if arc_count(n, f) == 0:            # f = 0: the path without ARC, bit for bit
+        return nnm_coord(rows, f, rule) if nnm else _coord(rows, plain)
+    C = _C_for(rows)
+    if rows.device.type == "cuda" and n <= MAX_ROWS:
+        ws = workspace(rows)
+        g = _gram_into(C, rows, ws)
+        Y = _padded_copy(rows.stacked())
+        np_ = C.gram_padded(n)
+        g2 = ws.get("arc_gram", np_ * np_) if nnm else None
+        arc_apply_into(C, ws, Y, g, n, f, 0, rows.d, g2)
+        out = torch.empty(rows.d, dtype=rows.dtype, device=rows.device)
+        if nnm:
+            nnm_coord_into(C, ws, Y, g2, n, f, rule, out)
+        else:
+            plain.into(C, Y, out)
+        return _finish(out, rows)
+    if rows.device.type == "cuda":      # beyond MAX_ROWS: the large kernels on the clipped copy
+        Y = _clipped_copy(rows, arc_scales_from_sqnorms(torch.diagonal(_large_gram(rows)), f))
+        if nnm:
+            return nnm_coord(replace(rows, obj=Y), f, rule)
+        if Y.dtype == torch.float16:
+            # gar_large.hip's radix select keys 16-bit rows by their top 16 bits, which is all of a bf16 but
+            # cuts an fp16's last 3 mantissa bits: the clipped fp16 values go in widened (exactly) instead
+            return _coord(replace(rows, obj=Y.float(), dtype=torch.float32), plain)
+        return _coord(replace(rows, obj=Y), plain)
+    s = _sqnorms(rows)
+    c = arc_scales_from_sqnorms(s, f)
+    Y = _clipped_copy(rows, c)
+    if not nnm:
+        return _coord(replace(rows, obj=Y), plain)
+    D = distances_from_gram(gram(rows)) if C is None or n > MAX_ROWS else C.cpu_pairwise(rows.obj)
+    return _finish(nnm_coord_from_distances(C, Y, arc_distances(D, s, c), f, rule), rows)
 
 
 def bulyan_weights(gradients, f: int, m: int | None = None) -> torch.Tensor:
@@ -886,6 +1022,22 @@ RULES = {
     "nnm-average": lambda gradients, f=0, **_: nnm(gradients, f, "average"),
     "nnm-trimmed-mean": lambda gradients, f, **_: nnm_coord(gradients, f, "trimmed-mean"),
     "nnm-median": lambda gradients, f=0, **_: nnm_coord(gradients, f, "median"),
+    "arc-krum": lambda gradients, f, m=None, **_: arc(gradients, f, "krum", m=m),
+    "arc-geomed": lambda gradients, f=0, iters=32, nu=1e-6, **_: arc(gradients, f, "geomed", iters=iters, nu=nu),
+    "arc-cclip": lambda gradients, f=0, tau=None, iters=3, start="mean", m=None, **_: arc(
+        gradients, f, "cclip", tau=tau, iters=iters, start=start, m=m),
+    "arc-dnc": lambda gradients, f=0, m=None, iters=16, **_: arc(gradients, f, "dnc", m=m, iters=iters),
+    "arc-average": lambda gradients, f=0, **_: arc(gradients, f, "average"),
+    "arc-nnm-krum": lambda gradients, f, m=None, **_: arc(gradients, f, "krum", True, m=m),
+    "arc-nnm-geomed": lambda gradients, f=0, iters=32, nu=1e-6, **_: arc(gradients, f, "geomed", True, iters=iters,
+                                                                         nu=nu),
+    "arc-nnm-cclip": lambda gradients, f=0, tau=None, iters=3, start="mean", m=None, **_: arc(
+        gradients, f, "cclip", True, tau=tau, iters=iters, start=start, m=m),
+    "arc-nnm-average": lambda gradients, f=0, **_: arc(gradients, f, "average", True),
+    "arc-trimmed-mean": lambda gradients, f, **_: arc_coord(gradients, f, "trimmed-mean"),
+    "arc-median": lambda gradients, f=0, **_: arc_coord(gradients, f, "median"),
+    "arc-nnm-trimmed-mean": lambda gradients, f, **_: arc_coord(gradients, f, "trimmed-mean", True),
+    "arc-nnm-median": lambda gradients, f=0, **_: arc_coord(gradients, f, "median", True),
     "condense": condense,
     "trimmed-mean": trimmed_mean,
     "averaged-median": averaged_median,

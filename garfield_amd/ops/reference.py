@@ -418,6 +418,84 @@ def nnm_coord(G, f: int, rule: str = "trimmed-mean") -> torch.Tensor:
     return trimmed_mean(Y, f) if rule == "trimmed-mean" else median(Y)
 
 
+def arc_count(n: int, f: int) -> int:
+    """Rows adaptive robust clipping may clip: k = (2 f (n - f)) // n (< n; 0 exactly when f = 0)."""
+    if not 0 <= f < n:
+        raise ValueError(f"arc: expected 0 <= f < n, got f = {f}, n = {n}")
+    return (2 * f * (n - f)) // n
+
+
+def arc_scales(sqnorms, f: int) -> torch.Tensor:
+    """The ARC scales [n] (fp32) from the squared norms s (docs/GAR_SEMANTICS.md "Adaptive robust clipping"):
+    C² = s of the row at position k of the order (s descending with a non-finite s as +inf, index
+    ascending); c_i = sqrt(C² / s_i) in fp64, rounded once to fp32, where s_i and C² are finite and
+    s_i > C²; 1 elsewhere."""
+    s = [float(v) for v in torch.as_tensor(sqnorms).detach().double().cpu().reshape(-1)]
+    n = len(s)
+    k = arc_count(n, f)
+    key = [v if math.isfinite(v) else math.inf for v in s]
+    c2 = key[sorted(range(n), key=lambda i: (-key[i], i))[k]]
+    c = [math.sqrt(c2 / s[i]) if math.isfinite(s[i]) and math.isfinite(c2) and s[i] > c2 else 1.0 for i in range(n)]
+    return torch.tensor(c, dtype=torch.float64).float()
+
+
+def arc_clip_rows(scales) -> list[int]:
+    """The rows ARC writes: those whose fp32 scale is not 1, ascending."""
+    return [i for i, c in enumerate(torch.as_tensor(scales).tolist()) if c != 1.0]
+
+
+def arc_gram(G: torch.Tensor, scales) -> torch.Tensor:
+    """The clipped rows' Gram (fp32): G'_ij = (c_i c_j) G_ij, the products in fp64 in that order, rounded once."""
+    c = torch.as_tensor(scales).detach().double().cpu()
+    cc = c[:, None] * c[None, :]
+    G = G.detach().cpu()
+    return torch.where(cc == 1.0, G.float(), (cc * G.double()).float())
+
+
+def arc_clip(X, f: int) -> torch.Tensor:
+    """The clipped rows y_i = c_i x_i [n, d] (fp64), the scales from the rows' own fp64 squared norms."""
+    X = _g(X)
+    return arc_scales((X * X).sum(1), f).double()[:, None] * X
+
+
+def arc_weights(X, f: int, rule: str = "krum", nnm: bool = False, **kw) -> torch.Tensor:
+    """Weights [n] (fp64) over the ORIGINAL rows of ``rule`` (krum / geomed / cclip / dnc / average) over the
+    clipped rows, behind the mixing when ``nnm``: w_j = c_j a_j."""
+    X = _g(X)
+    n = X.shape[0]
+    c = arc_scales((X * X).sum(1), f).double()
+    D = pairwise_sqdist(c[:, None] * X)
+    if nnm:
+        a = nnm_weights(D, f, rule, **kw).double()
+    elif rule == "krum":
+        a = krum_weights(D, f, kw.get("m"))
+    elif rule == "geomed":
+        a = geomed_weights(D, kw.get("iters", 32), kw.get("nu", 1e-6))
+    elif rule == "cclip":
+        a0 = krum_weights(D, f, kw.get("m")) if kw.get("start", "mean") == "krum" else None
+        a = cclip_weights(D, n, a0, kw.get("tau"), f, kw.get("iters", 3))
+    elif rule == "dnc":
+        a = dnc_weights(D, n - f if kw.get("m") is None else kw["m"], kw.get("iters", 16))[0]
+    elif rule == "average":
+        a = torch.full((n,), 1.0 / n, dtype=torch.float64)
+    else:
+        raise ValueError(f"arc: unsupported rule {rule!r} (krum, geomed, cclip, dnc, average)")
+    return c * a.double()
+
+
+def arc(X, f: int, rule: str = "krum", nnm: bool = False, **kw) -> torch.Tensor:
+    return combine(X, arc_weights(X, f, rule, nnm, **kw))
+
+
+def arc_coord(X, f: int, rule: str = "trimmed-mean", nnm: bool = False) -> torch.Tensor:
+    """A coordinate-wise rule (trimmed-mean with the same f, or median) over the clipped rows, behind the
+    mixing when ``nnm``."""
+    Y = arc_clip(X, f)
+    if nnm:
+        return nnm_coord(Y, f, rule)
+    return trimmed_mean(Y, f) if rule == "trimmed-mean" else median(Y)
+
+
 def bulyan_weights(D: torch.Tensor, f: int, m: int | None = None) -> torch.Tensor:
     n = D.shape[0]
     m = n - f - 2 if m is None else m

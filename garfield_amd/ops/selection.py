@@ -11,7 +11,9 @@ and nowhere else:
   ``gpu_*_select`` kernels on a device Gram, n <= MAX_ROWS, flat or batched over segments),
   :meth:`~Selection.on_host` (fp64 squared distances: the C++ functions, else the oracle of
   ``ops/reference.py``) and :meth:`~Selection.from_gram` (vectorised on the Gram's own device, any n);
-* ``pre="nnm"`` wraps each of them in the mix -> selection on the mixed rows -> un-mix sandwich.
+* ``pre="nnm"`` wraps each of them in the mix -> selection on the mixed rows -> un-mix sandwich;
+  ``pre="arc"`` in adaptive robust clipping (scale the Gram -> selection on the clipped rows -> fold the
+  scales into the weights), ``pre="arc+nnm"`` in both, the clipping outermost.
 
 A new distance rule is one ``_Rule`` entry in :data:`TABLE` plus its arguments in :func:`resolve`;
 ``ops/gar.py`` and the engines only pick the backend.
@@ -30,6 +32,10 @@ from garfield_amd.ops import reference as ref
 MAX_ROWS = 128
 CCLIP_STARTS = ("mean", "krum")
 NNM_RULES = ("krum", "geomed", "cclip", "average")
+ARC_RULES = ("krum", "geomed", "cclip", "dnc", "average")
+# the pre-aggregations: the rules each takes, and its prefix in the registry's names and in messages
+PRE_RULES = {"nnm": NNM_RULES, "arc": ARC_RULES, "arc+nnm": NNM_RULES}
+PRE_TAGS = {"nnm": "nnm", "arc": "arc", "arc+nnm": "arc-nnm"}
 BRUTE_MAX_SUBSETS = 2 ** 32
 
 
@@ -242,6 +248,55 @@ def nnm_fold(S: torch.Tensor, a: torch.Tensor, c: int) -> torch.Tensor:
     return (acc / a.sum().clamp(min=torch.finfo(torch.float64).tiny) / c).float()
 
 
+def arc_count(n: int, f: int) -> int:
+    """Rows adaptive robust clipping may clip: k = (2 f (n - f)) // n (< n; 0 exactly when f = 0)."""
+    return (2 * f * (n - f)) // n
+
+
+def arc_scales_from_sqnorms(s: torch.Tensor, f: int) -> torch.Tensor:
+    """The ARC scales [n] (fp32, s's device) from the squared norms ``s`` (a Gram's diagonal), vectorised, any n,
+    no host round trip: reference.arc_scales with the rank counted as k_arc_scale counts it. From the same
+    fp32 diagonal: the kernel's bits (fp64 ``/`` and ``sqrt``, rounded once)."""
+    n = s.numel()
+    k = arc_count(n, f)
+    if k == 0:
+        return torch.ones(n, dtype=torch.float32, device=s.device)
+    key = torch.where(torch.isfinite(s), s, torch.full_like(s, math.inf))
+    ids = torch.arange(n, device=s.device)
+    before = (key[None, :] > key[:, None]) | ((key[None, :] == key[:, None]) & (ids[None, :] < ids[:, None]))
+    c2 = torch.where(before.sum(1) == k, key, torch.full_like(key, -math.inf)).max()
+    clip = torch.isfinite(s) & torch.isfinite(c2) & (s > c2)
+    one = torch.ones((), dtype=torch.float64, device=s.device)
+    return torch.where(clip, (c2.double() / torch.where(clip, s.double(), one)).sqrt(), one).float()
+
+
+def arc_gram(g: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """The clipped rows' Gram G'_ij = (c_i c_j) G_ij in g's dtype (the product in fp64, rounded once)."""
+    cc = c.double()[:, None] * c.double()[None, :]
+    return torch.where(cc == 1.0, g, (cc * g.double()).to(g.dtype))
+
+
+def arc_fold(c: torch.Tensor, a: torch.Tensor) -> torch.Tensor:
+    """w_j = c_j a_j (fp64 product, as fp32): the weights over the clipped rows onto the original rows."""
+    return (c.to(a.device).double() * a.double()).float()
+
+
+def arc_distances(D: torch.Tensor, s: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """The clipped rows' squared distances (fp64, +inf diagonal) from the rows' distances ``D``, their squared
+    norms ``s`` and the scales ``c``: G_ij = (s_i + s_j - D_ij) / 2, D'_ij = c_i² s_i + c_j² s_j - 2 c_i c_j G_ij.
+    Squared distances lose the norms, so the host backend carries ``s`` beside ``D``; both are additive over
+    coordinate shards. A pair of unclipped rows keeps its entry bit for bit."""
+    D, s, c = D.double().cpu(), s.double().cpu(), c.double().cpu()
+    G = 0.5 * (s[:, None] + s[None, :] - D)
+    cc = c[:, None] * c[None, :]
+    sc = c * c * s
+    Dc = (sc[:, None] + sc[None, :] - 2.0 * cc * G)
+    Dc = torch.where(torch.isfinite(Dc), Dc.clamp(min=0), torch.full_like(Dc, math.inf))
+    Dc = torch.where((cc == 1.0) | ~torch.isfinite(D), D, Dc)
+    Dc.fill_diagonal_(math.inf)
+    return Dc
+
+
 # --------------------------------------------------------------------------- #
 # The table: per rule, the selection on each backend. ``s`` is the resolved Selection.
 #   device(s, C, gram, ws, batch) -> w [batch * n] in the buffers of ``ws`` (Bulyan: W [batch * t * n])
@@ -427,7 +482,8 @@ class Selection:
     tau: float = 0.0           # cclip: the radius as the launchers take it, 0 = from the data
     start: object = "mean"     # cclip: "mean", "krum", "center" (the appended row nw) or an [n] weight tensor
     nw: int | None = None      # cclip: rows 0..nw-1 are workers, the rest basis-only
-    pre: str | None = None     # "nnm": the rule runs on the rows mixed over their n - f nearest
+    pre: str | None = None     # "nnm": the rule runs on the rows mixed over their n - f nearest; "arc": on the rows
+                               # clipped to the (k + 1)-th largest norm; "arc+nnm": clipped, then mixed
 
     @property
     def t(self) -> int:
@@ -448,42 +504,79 @@ class Selection:
         e = self._entry
         return e.gram is not None and (cuda or e.gram_on_cpu)
 
+    @property
+    def mixes(self) -> bool:
+        """Whether nearest-neighbour mixing runs in front of the rule."""
+        return self.pre in ("nnm", "arc+nnm")
+
+    @property
+    def clips(self) -> int:
+        """The rows adaptive robust clipping may clip in front of everything else (0: no clipping, and no
+        trace of it: with f = 0 every path is the path without ARC, bit for bit)."""
+        return arc_count(self.n, self.f) if self.pre in ("arc", "arc+nnm") else 0
+
     def on_device(self, C, gram: torch.Tensor, ws, batch: int = 1) -> torch.Tensor:
         """Weights [n] ([batch, n]; Bulyan: W [t, n] / [batch, t, n]) from ``batch`` device Grams (pitch
         gram_padded(n), n <= device_rows) by the ``gpu_*_select`` launches. Every buffer comes from ``ws``
-        (a ``gar.Workspace``, allocated on the first call: capture-safe after it). With ``pre="nnm"``:
-        k_nnm_mix -> the rule's selection on the pseudo-Gram -> k_nnm_unmix."""
+        (a ``gar.Workspace``, allocated on the first call: capture-safe after it). The sandwich around the
+        rule: k_arc_scale (``pre`` "arc" / "arc+nnm") -> k_nnm_mix ("nnm" / "arc+nnm") -> the rule's selection
+        on the Gram it is handed -> k_nnm_unmix -> k_arc_fold."""
         n, f = self.n, self.f
-        if self.pre is None:
-            return self._entry.device(self, C, gram, ws, batch)
         np_ = C.gram_padded(n)
-        H = _buf(ws, batch, "nnm_H", np_ * np_)
-        masks = _buf(ws, batch, "nnm_masks", 2 * n, torch.int64)
-        C.gpu_nnm_mix(gram, n, f, H, masks, batch)
-        a = self._entry.device(self, C, H, ws, batch)
-        w = _buf(ws, batch, "nnm_w", n)
-        C.gpu_nnm_unmix(a, masks, n, f, w, batch)
+        scales = None
+        if self.clips:
+            scales = _buf(ws, batch, "arc_scales", n)
+            G2 = _buf(ws, batch, "arc_gram", np_ * np_)
+            C.gpu_arc_scale(gram, n, f, scales, _buf(ws, batch, "arc_clip_rows", n + 1, torch.int32), G2, batch)
+            gram = G2
+        if self.mixes:
+            H = _buf(ws, batch, "nnm_H", np_ * np_)
+            masks = _buf(ws, batch, "nnm_masks", 2 * n, torch.int64)
+            C.gpu_nnm_mix(gram, n, f, H, masks, batch)
+            a = self._entry.device(self, C, H, ws, batch)
+            w = _buf(ws, batch, "nnm_w", n)
+            C.gpu_nnm_unmix(a, masks, n, f, w, batch)
+        else:
+            w = self._entry.device(self, C, gram, ws, batch)
+        if scales is not None:
+            a, w = w, _buf(ws, batch, "arc_w", n)
+            C.gpu_arc_fold(a, scales, n, w, batch)
         return w
 
-    def on_host(self, C, D: torch.Tensor) -> torch.Tensor:
+    def on_host(self, C, D: torch.Tensor, sqnorms: torch.Tensor | None = None) -> torch.Tensor:
         """Weights [n] (fp32, CPU; Bulyan: W [t, n]) from fp64 squared distances: the C++ functions of the
-        extension ``C``, else (``C`` None, or more rows than they take) the oracle."""
+        extension ``C``, else (``C`` None, or more rows than they take) the oracle. ARC needs the rows'
+        squared norms ``sqnorms`` [n] beside ``D`` (distances lose them)."""
         n, f = self.n, self.f
-        if self.pre is None:
-            return self._entry.host(self, C, D)
-        if C is None or n > MAX_ROWS:   # the C++ sets are two mask words
-            return ref.nnm_weights(D, f, self.rule, m=self.m, iters=self.iters, nu=self.nu,
-                                   tau=self.tau if self.tau > 0 else None, start=self.start)
-        Dm, masks = C.cpu_nnm_mix(D, f)
-        return C.cpu_nnm_unmix(self._entry.host(self, C, Dm), masks, n - f)
+        c = None
+        if self.clips:
+            if sqnorms is None:
+                raise ValueError("arc: the host selection needs the rows' squared norms beside their distances")
+            c = arc_scales_from_sqnorms(sqnorms.detach().cpu(), f)
+            D = arc_distances(D, sqnorms, c)
+        if not self.mixes:
+            w = self._entry.host(self, C, D)
+        elif C is None or n > MAX_ROWS:   # the C++ sets are two mask words
+            w = ref.nnm_weights(D, f, self.rule, m=self.m, iters=self.iters, nu=self.nu,
+                                tau=self.tau if self.tau > 0 else None, start=self.start)
+        else:
+            Dm, masks = C.cpu_nnm_mix(D, f)
+            w = C.cpu_nnm_unmix(self._entry.host(self, C, Dm), masks, n - f)
+        return w if c is None else arc_fold(c, w)
 
     def from_gram(self, g: torch.Tensor) -> torch.Tensor:
         """Weights [n] (fp32; Bulyan: W [t, n]) vectorised on the device of the Gram ``g`` (any n, no host
         round trip; Krum and Bulyan on the GPU: gar_large.hip)."""
-        if self.pre is None:
-            return self._entry.gram(self, g)
-        H, S = nnm_from_gram(g, self.f)
-        return nnm_fold(S, self._entry.gram(self, H), self.n - self.f)
+        c = None
+        if self.clips:
+            c = arc_scales_from_sqnorms(torch.diagonal(g), self.f)
+            g = arc_gram(g, c)
+        if self.mixes:
+            H, S = nnm_from_gram(g, self.f)
+            w = nnm_fold(S, self._entry.gram(self, H), self.n - self.f)
+        else:
+            w = self._entry.gram(self, g)
+        return w if c is None else arc_fold(c, w)
 
 
 def resolve(rule: str, n: int, f: int, m: int | None = None, pre: str | None = None,
@@ -494,20 +587,22 @@ def resolve(rule: str, n: int, f: int, m: int | None = None, pre: str | None = N
     start = kw.get("start")
     start = "mean" if start is None else start
     if pre is not None:
+        tag = PRE_TAGS.get(pre, "nnm")
         if rule == "cclip" and not isinstance(start, str):
-            raise ValueError(f"nnm-cclip: start must be one of {CCLIP_STARTS}")
-        if pre != "nnm":
-            raise ValueError(f"unknown pre-aggregation {pre!r}; available: 'nnm'")
-        if rule not in NNM_RULES:
-            raise ValueError(f"nnm: unsupported rule {rule!r}; available: {NNM_RULES}")
+            raise ValueError(f"{tag}-cclip: start must be one of {CCLIP_STARTS}")
+        if pre not in PRE_RULES:
+            raise ValueError(f"unknown pre-aggregation {pre!r}; available: {tuple(PRE_RULES)}")
+        if rule not in PRE_RULES[pre]:
+            raise ValueError(f"{tag}: unsupported rule {rule!r}; available: {PRE_RULES[pre]}")
         if not 0 <= f < n:
-            raise ValueError(f"nnm: expected 0 <= f < n, got f = {f}, n = {n}")
+            raise ValueError(f"{tag}: expected 0 <= f < n, got f = {f}, n = {n}")
     elif rule not in TABLE:
         raise ValueError(f"unknown distance-based rule {rule!r}; available: {tuple(TABLE)}")
     if rule in ("krum", "bulyan"):
         m = n - f - 2 if m is None else m
         if pre is not None and (n < 2 * f + 3 or not 1 <= m <= n - f - 2):   # Krum's own requirement, as on every other path
-            raise ValueError(f"nnm-krum: expected n >= 2f + 3 and 1 <= m <= n - f - 2, got n = {n}, f = {f}, m = {m}")
+            raise ValueError(f"{PRE_TAGS[pre]}-krum: expected n >= 2f + 3 and 1 <= m <= n - f - 2, got n = {n}, f = {f}, "
+                             f"m = {m}")
         return Selection(rule, n, f, m=m, pre=pre)
     if rule == "geomed":
         return Selection(rule, n, f, iters=int(kw.get("iters", 32)), nu=float(kw.get("nu", 1e-6)), pre=pre)
@@ -520,7 +615,7 @@ def resolve(rule: str, n: int, f: int, m: int | None = None, pre: str | None = N
         m = n - f if m is None else m
         if not 1 <= m <= n:
             raise ValueError(f"dnc: expected 1 <= m <= n, got m = {m}, n = {n}")
-        return Selection(rule, n, f, m=int(m), iters=iters)
+        return Selection(rule, n, f, m=int(m), iters=iters, pre=pre)
     if rule == "cclip":
         iters, tau = kw.get("iters", 3), kw.get("tau")
         if iters is None or int(iters) < 1:

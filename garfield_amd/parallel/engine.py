@@ -58,6 +58,11 @@ COORD_RULES = {"median", "trimmed-mean", "averaged-median", "average-nan", "cond
 # coordinate-wise rules accepted behind pre_aggregation="nnm" (gar.nnm_coord; "nnm-median" exists through
 # the functional interface and the registry only)
 NNM_ENGINE_COORD_RULES = ("trimmed-mean",)
+# coordinate-wise rules accepted behind pre_aggregation="arc": the clipped rows are rewritten, the plain rule runs
+ARC_ENGINE_COORD_RULES = ("trimmed-mean", "median")
+# per pre-aggregation: the rules the engine takes behind it
+PRE_ENGINE_RULES = {"nnm": gar.NNM_RULES + NNM_ENGINE_COORD_RULES, "arc": gar.ARC_RULES + ARC_ENGINE_COORD_RULES,
+                    "arc+nnm": gar.NNM_RULES + NNM_ENGINE_COORD_RULES}
 LAYERWISE_RULES = set(selection.TABLE) | {"aksel"}   # per-layer != flat only for distance-based rules
 # Layer-wise Krum as device operations (gar_layerwise.hip: one segmented Gram launch, a batched
 # selection, one segmented combine + SGD); "0" runs the per-segment loop (the reference form).
@@ -100,6 +105,11 @@ class EngineConfig:
     # over the n set means, which are never stored (gar.nnm_coord), on the same paths. Not yet supported
     # (ValueError at construction): any other rule (median and bulyan included), layerwise=True, and the
     # sharded path with n > 128 rows on the GPU. None: exactly today's paths.
+    # "arc": adaptive robust clipping before the rule (the 2f(n - f) // n rows of largest norm scaled down to
+    # the next one's norm; docs/GAR_SEMANTICS.md), folded into the Gram and the row weights for gar in
+    # {krum, geomed, cclip, dnc, average}; gar in {trimmed-mean, median} gets the clipped exchange rows
+    # rewritten in place, then runs unchanged. "arc+nnm": ARC, then NNM, then the rule, for what "nnm" takes.
+    # Same paths and the same refusals as "nnm".
     pre_aggregation: str | None = None
     workers_per_rank: int = 8
     lr: float = 0.1
@@ -430,23 +440,35 @@ class RobustDataParallel:
         cfg = self.cfg
         if cfg.pre_aggregation is None:
             return
-        if cfg.pre_aggregation != "nnm":
-            raise ValueError(f"unknown pre_aggregation {cfg.pre_aggregation!r}; available: 'nnm'")
-        if cfg.gar not in gar.NNM_RULES + NNM_ENGINE_COORD_RULES:
-            raise ValueError(f"pre_aggregation='nnm' is not yet supported with gar={cfg.gar!r}; "
-                             f"available: {gar.NNM_RULES + NNM_ENGINE_COORD_RULES}")
+        pre = cfg.pre_aggregation
+        if pre not in PRE_ENGINE_RULES:
+            raise ValueError(f"unknown pre_aggregation {pre!r}; available: {tuple(PRE_ENGINE_RULES)}")
+        if cfg.gar not in PRE_ENGINE_RULES[pre]:
+            raise ValueError(f"pre_aggregation={pre!r} is not yet supported with gar={cfg.gar!r}; "
+                             f"available: {PRE_ENGINE_RULES[pre]}")
         if cfg.layerwise:
-            raise ValueError("pre_aggregation='nnm' is not yet supported with layerwise=True")
+            raise ValueError(f"pre_aggregation={pre!r} is not yet supported with layerwise=True")
         if (self.device.type == "cuda" and cfg.workers_per_rank * self.ctx.world_size > gar.MAX_ROWS
                 and self._want_sharded()):
-            raise ValueError(f"pre_aggregation='nnm' is not yet supported by the sharded aggregation of more than "
+            raise ValueError(f"pre_aggregation={pre!r} is not yet supported by the sharded aggregation of more than "
                              f"{gar.MAX_ROWS} rows (shard_gar=False runs the unsharded path)")
+
+    def _pre_name(self) -> str:
+        """The registry's prefix of the configured pre-aggregation ("", "nnm-", "arc-", "arc-nnm-")."""
+        pre = self.cfg.pre_aggregation
+        return selection.PRE_TAGS[pre] + "-" if pre else ""
+
+    def _pre_stages(self, n: int) -> tuple:
+        """(rows ARC may clip, whether NNM mixes) of the configured pre-aggregation over ``n`` rows."""
+        pre = self.cfg.pre_aggregation
+        clips = selection.arc_count(n, self.cfg.f) if pre in ("arc", "arc+nnm") else 0
+        return clips, pre in ("nnm", "arc+nnm")
 
     def _selection(self, n: int):
         """The configured rule's resolved selection over ``n`` rows (ops/selection.py); None for a rule that
         is not a distance-based selection (coordinate-wise, the plain average, Aksel)."""
         cfg = self.cfg
-        if cfg.gar in selection.TABLE or (cfg.pre_aggregation and cfg.gar in gar.NNM_RULES):
+        if cfg.gar in selection.TABLE or cfg.gar in selection.PRE_RULES.get(cfg.pre_aggregation, ()):
             return selection.resolve(cfg.gar, n, cfg.f, cfg.m, cfg.pre_aggregation, cfg.gar_kwargs)
         return None
 
@@ -472,7 +494,7 @@ class RobustDataParallel:
     def _check_gar(self) -> None:
         from garfield_amd import aggregators
 
-        rule = aggregators.get(("nnm-" if self.cfg.pre_aggregation else "") + self.cfg.gar)
+        rule = aggregators.get(self._pre_name() + self.cfg.gar)
         kw = dict(self.cfg.gar_kwargs)
         if self.cfg.m is not None:
             kw["m"] = self.cfg.m
@@ -651,11 +673,20 @@ class RobustDataParallel:
         """The configured coordinate-wise rule (or Bulyan) over ``G`` (the [n, d] exchange rows or a list of
         rows) into the fp32 vector ``out``."""
         C, f, n = self._C, self.cfg.f, len(G)
-        if self.cfg.pre_aggregation:   # Gram -> sets -> k_nnm_coord: the rule over the n set means, never stored
+        if self.cfg.pre_aggregation:
+            clips, mixes = self._pre_stages(n)
             rows = gar.prepare(G)
             ws = gar.workspace(rows)
-            gar.nnm_coord_into(C, ws, rows.obj, gar._gram_into(C, rows, ws), n, f, self.cfg.gar, out)
-            return out
+            g = gar._gram_into(C, rows, ws) if clips or mixes else None
+            if clips:   # Gram -> k_arc_scale -> k_arc_apply: the clipped rows rewritten in place, then the rule as without
+                np_ = C.gram_padded(n)
+                g2 = ws.get("arc_gram", np_ * np_) if mixes else None
+                gar.arc_apply_into(C, ws, rows.obj, g, n, f, 0, rows.d, g2)
+                g = g2
+            if mixes:   # Gram -> sets -> k_nnm_coord: the rule over the n set means, never stored
+                gar.nnm_coord_into(C, ws, rows.obj, g, n, f, self.cfg.gar, out)
+                return out
+            G = rows.obj
         if self.cfg.gar == "bulyan":
             return gar.bulyan_tail_into(C, G, self._weights(G), n, f, out)
         cr = self._coord if n == self.n else self._coord_rule(n)   # an explicit row list may be any subset
@@ -664,15 +695,17 @@ class RobustDataParallel:
         return cr.into(C, G, out, self.cfg.seed + self.step_count)
 
     def _rule_name(self) -> str:
-        """The rule's name in gar.RULES: a coordinate-wise rule behind the mixing is its "nnm-" entry."""
+        """The rule's name in gar.RULES: a coordinate-wise rule behind a pre-aggregation is its "nnm-" / "arc-" /
+        "arc-nnm-" entry."""
         cfg = self.cfg
-        return ("nnm-" + cfg.gar) if cfg.pre_aggregation and cfg.gar in NNM_ENGINE_COORD_RULES else cfg.gar
+        return (self._pre_name() + cfg.gar) if cfg.gar in ARC_ENGINE_COORD_RULES else cfg.gar
 
     def _rule_kwargs(self) -> dict:
         """The keyword arguments with which the configured rule runs by name (gar.aggregate)."""
         cfg = self.cfg
         if self._coord is not None:
-            return self._coord.kwargs(cfg.seed + self.step_count)
+            kw = self._coord.kwargs(cfg.seed + self.step_count)
+            return {**kw, "f": cfg.f} if cfg.pre_aggregation else kw   # the clipping and the mixing take f under any rule
         kw = dict(cfg.gar_kwargs)
         if cfg.gar != "average":
             kw["f"] = cfg.f

@@ -551,6 +551,14 @@ class ShardedAggregator:
         shadow = e._shadow[b.own] if e._shadow is not None else None
         return e.flat.data[b.own], mom, shadow
 
+    def _pre_aggregates(self, cfg) -> bool:
+        """Whether the configured pre-aggregation does anything in front of the rule. ARC with f = 0 in front of
+        a coordinate-wise rule clips nothing: the step is the one without it, with no Gram and no all-reduce."""
+        if not cfg.pre_aggregation:
+            return False
+        clips, mixes = self.e._pre_stages(self.n)
+        return bool(clips or mixes or self.e._sel is not None)
+
     def _aggregate_update(self, aggregate, first: bool, staged: bool = False) -> None:
         """Every bucket, in update order: ``aggregate(b)`` returns the owned shard's aggregate as one vector
         (usually written into b's scratch vector, ``_gagg``), b is updated from it and its weights are
@@ -562,7 +570,7 @@ class ShardedAggregator:
             return self._gpu_large(cfg, first)
         e, C = self.e, self.e._C
         rule, f, n = cfg.gar, cfg.f, self.n
-        if rule in DISTANCE_RULES or rule == "aksel" or cfg.pre_aggregation:
+        if rule in DISTANCE_RULES or rule == "aksel" or self._pre_aggregates(cfg):
             total = None
             slabs = []
             for b in self.buckets:   # partial statistics as the buckets land
@@ -582,17 +590,34 @@ class ShardedAggregator:
             else:
                 total = self._sum_over_ranks(total)
                 if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:
-                    # the sets once from the summed Gram, identical on every rank; then per bucket the rule
-                    # over the n set means of the owned coordinates (never stored), as Bulyan's tail below
-                    masks = self._ws_any().get("nnm_masks", 2 * n, torch.int64)
-                    C.gpu_nnm_sets(total, n, f, masks)
+                    # the scales and the sets once from the summed Gram, identical on every rank; then per bucket
+                    # the clipped rows of the owned coordinates rewritten in place and the rule over them, or over
+                    # their n set means (never stored), as Bulyan's tail below
+                    clips, mixes = e._pre_stages(n)
+                    wsa = self._ws_any()
+                    if clips:
+                        np_ = C.gram_padded(n)
+                        scales = wsa.get("arc_scales", n)
+                        clip_rows = wsa.get("arc_clip_rows", n + 1, torch.int32)
+                        clipped = wsa.get("arc_gram", np_ * np_) if mixes else None
+                        C.gpu_arc_scale(total, n, f, scales, clip_rows, clipped)
+                        total = clipped
+                    if mixes:
+                        masks = wsa.get("nnm_masks", 2 * n, torch.int64)
+                        C.gpu_nnm_sets(total, n, f, masks)
                     e.last_weights = None
+                    seed = cfg.seed + e.step_count
 
-                    def mixed(b):
+                    def pre_aggregated(b):
                         g = self._gagg(b)
-                        C.gpu_nnm_coord(b.rows, masks, n, f, rule, g)
+                        if clips:
+                            C.gpu_arc_apply(b.rows, scales, clip_rows, f, 0, b.S)
+                        if mixes:
+                            C.gpu_nnm_coord(b.rows, masks, n, f, rule, g)
+                        else:
+                            e._coord.into(C, b.rows, g, seed + 7919 * b.lo)
                         return g
-                    self._aggregate_update(mixed, first, True)
+                    self._aggregate_update(pre_aggregated, first, True)
                     return
                 if n > e._sel.device_rows:
                     raise ValueError(f"{rule}: n must be <= {e._sel.device_rows} on the GPU")
@@ -844,7 +869,7 @@ class ShardedAggregator:
         e = self.e
         rule, f = cfg.gar, cfg.f
         n = self.n
-        if rule in DISTANCE_RULES or rule == "aksel" or cfg.pre_aggregation:
+        if rule in DISTANCE_RULES or rule == "aksel" or self._pre_aggregates(cfg):
             C = _native.require_for(X.device)
             if rule == "aksel":
                 med = gar.aggregate("median", X)
@@ -852,10 +877,19 @@ class ShardedAggregator:
                 w = gar.aksel_weights_from_distances(dist_, gar.aksel_count(n, f, cfg.gar_kwargs.get("mode", "mid")))
             else:
                 D = self._sum_over_ranks(gar.pairwise_distances(X))
-                if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:   # the same sets on every rank, no weights
+                clips, mixes = e._pre_stages(n)
+                # ARC decides from the norms, which the distances lose: they are summed over ranks beside D
+                sq = self._sum_over_ranks((X.double() ** 2).sum(1)) if clips else None
+                if cfg.pre_aggregation and rule in gar.NNM_COORD_RULES:   # the same scales and sets on every rank, no weights
                     e.last_weights = None
-                    return gar.nnm_coord_from_distances(C, X, D, f, rule)
-                w = e._sel.on_host(C, D)   # on the summed distances: the same selection on every rank
+                    if clips:
+                        c = gar.arc_scales_from_sqnorms(sq, f)
+                        X = gar._clipped_copy(gar.prepare(X), c)
+                        D = gar.arc_distances(D, sq, c)
+                    if mixes:
+                        return gar.nnm_coord_from_distances(C, X, D, f, rule)
+                    return gar.aggregate(rule, X, **e._coord.kwargs(cfg.seed + e.step_count)).float()
+                w = e._sel.on_host(C, D, sq)   # on the summed distances: the same selection on every rank
                 if rule == "bulyan":
                     e.last_weights = None
                     return gar.bulyan_tail_host(C, X, w, n, f)

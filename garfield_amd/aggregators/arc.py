@@ -9,6 +9,7 @@ mixing's) runs on it."""
 from garfield_amd.aggregators import register
 from garfield_amd.aggregators._common import n_of
 from garfield_amd.aggregators.average import check as _average_check
+from garfield_amd.aggregators.caf import check as _caf_check
 from garfield_amd.aggregators.cclip import check as _cclip_check
 from garfield_amd.aggregators.dnc import check as _dnc_check
 from garfield_amd.aggregators.geomed import check as _geomed_check
@@ -25,7 +26,9 @@ def _check_clip(gradients, f):
     return None
 
 
-def _rule_kwargs(rule, m=None, iters=None, nu=1e-6, tau=None, start=None, **kwargs):
+def _rule_kwargs(rule, m=None, iters=None, nu=1e-6, tau=None, start=None, max_passes=None, **kwargs):
+    if rule == "caf":
+        return {"iters": 16 if iters is None else iters, "max_passes": max_passes}
     if rule == "cclip":
         return {"m": m, "iters": 3 if iters is None else iters, "tau": tau, "start": "mean" if start is None else start}
     return {"krum": {"m": m}, "geomed": {"iters": 32 if iters is None else iters, "nu": nu},
@@ -86,3 +89,4 @@ for _nnm in (False, True):
     _make_coord("trimmed-mean", _trimmed_mean_check, _nnm)
     _make_coord("median", _median_check, _nnm)
 _make("dnc", _dnc_check, False)
+_make("caf", _caf_check, False)

@@ -167,6 +167,18 @@ class DnCGAR(_GAR):
         return kw
 
 
+class CAFGAR(_GAR):
+    """CAF covariance filter (new, absent from the reference); ``iters:<int>`` and ``max_passes:<int>`` (0: n) optional."""
+    rule_name = "caf"
+    defaults = {"iters": 16, "max_passes": 0}
+
+    def kwargs(self):
+        kw = {"iters": int(self.args["iters"])}
+        if self.args["max_passes"]:
+            kw["max_passes"] = int(self.args["max_passes"])
+        return kw
+
+
 class NNMKrumGAR(KrumGAR):
     """Multi-Krum after nearest-neighbour mixing over the n - f nearest (new, absent from the reference)."""
     rule_name = "nnm-krum"
@@ -198,5 +210,5 @@ for _name, _cls in (("average", AverageGAR), ("average-nan", AverageNaNGAR), ("m
                     ("condense", CondenseGAR), ("trimmed-mean", TrimmedMeanGAR),
                     ("geomed", GeoMedGAR), ("nnm-krum", NNMKrumGAR), ("nnm-geomed", NNMGeoMedGAR),
                     ("nnm-average", NNMAverageGAR), ("cclip", CClipGAR), ("nnm-cclip", NNMCClipGAR),
-                    ("dnc", DnCGAR)):
+                    ("dnc", DnCGAR), ("caf", CAFGAR)):
     register(_name, _cls)

@@ -44,11 +44,12 @@ def add_common(p: argparse.ArgumentParser, ps: bool = True) -> argparse.Argument
     p.add_argument("--num_iter", type=int, default=5000)
     p.add_argument("--gar", type=str, default="average",
                    help="GAR name (garfield_amd.aggregators.gars): average, median, krum, bulyan, brute, aksel, condense, "
-                        "trimmed-mean, averaged-median, average-nan, geomed, cclip, dnc (DnC spectral filtering), nnm-*, arc-*")
+                        "trimmed-mean, averaged-median, average-nan, geomed, cclip, dnc (DnC spectral filtering), "
+                        "caf (CAF covariance filter), nnm-*, arc-*")
     p.add_argument("--pre_aggregation", type=str, default=None, choices=["nnm", "arc", "arc+nnm"],
                    help="nnm: nearest-neighbour mixing before --gar (krum, geomed, cclip, average): every gradient is "
                         "replaced by the mean of its n - f nearest, for heterogeneous (--non_iid) data; arc: adaptive "
-                        "robust clipping before --gar (also dnc, trimmed-mean, median): the 2f(n - f) // n gradients of "
+                        "robust clipping before --gar (also dnc, caf, trimmed-mean, median): the 2f(n - f) // n gradients of "
                         "largest norm are scaled down to the next one's norm; arc+nnm: the clipping, then the mixing")
     p.add_argument("--acc_freq", type=int, default=100, help="Accuracy evaluation period (iterations).")
     p.add_argument("--bench", type=str2bool, default=False, help="Print per-step timing and bandwidth.")

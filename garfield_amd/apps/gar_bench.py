@@ -24,8 +24,8 @@ from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
          "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average", "cclip", "cclip-krum", "nnm-cclip",
-         "nnm-trimmed-mean", "nnm-median", "dnc",
-         "arc-krum", "arc-geomed", "arc-cclip", "arc-dnc", "arc-average", "arc-nnm-krum", "arc-nnm-geomed",
+         "nnm-trimmed-mean", "nnm-median", "dnc", "caf",
+         "arc-krum", "arc-geomed", "arc-cclip", "arc-dnc", "arc-caf", "arc-average", "arc-nnm-krum", "arc-nnm-geomed",
          "arc-nnm-cclip", "arc-nnm-average", "arc-trimmed-mean", "arc-median", "arc-nnm-trimmed-mean", "arc-nnm-median"]
 # "cclip-krum": centered clipping from the Multi-Krum start (start="krum"), Krum's f
 

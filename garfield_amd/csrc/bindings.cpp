@@ -2144,6 +2144,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
      "DnC spectral-filtering weights (power rounds on the doubly centred distances of the Gram) on device; scores = "
      "the squared projection of every row on the top principal direction; batch > 1: gram [batch, np, np] -> "
      "weights / scores [batch, n]");
+  m.def("gpu_caf_select", [](const at::Tensor& gram, int n, int f, int iters, int max_passes, const at::Tensor& w,
+                             const at::Tensor& lams, int batch) {
+    const int np = check_select("gpu_caf_select", gram, n, batch, {{w, n}, {lams, n}});
+    TORCH_CHECK(f >= 0 && n >= 2 * f + 1 && iters >= 1 && max_passes >= 0,
+                "gpu_caf_select: 0 <= f, n >= 2f + 1, iters >= 1 and max_passes >= 0 (0 = n)");
+    c10::hip::HIPGuard guard(gram.device().index());
+    garfield::gpu::caf_select(fptr(gram), np, n, f, iters, max_passes, fptr(w), fptr(lams), stream_of(gram.device()),
+                              batch);
+  }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("iters"), py::arg("max_passes"), py::arg("weights"),
+     py::arg("lams"), py::arg("batch") = 1,
+     "CAF covariance-filter weights (passes of power rounds on the weighted, centred distances of the Gram) on device; "
+     "lams = the top eigenvalue of the weighted covariance per pass, +inf beyond the last; max_passes 0 = n; "
+     "batch > 1: gram [batch, np, np] -> weights / lams [batch, n]");
   m.def("gpu_nnm_mix", [](const at::Tensor& gram, int n, int f, const at::Tensor& H, const at::Tensor& masks,
                           int batch) {
     const int64_t hp = garfield::gpu::gram_padded(n);   // H has the Gram's shape
@@ -2975,6 +2988,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return py::make_tuple(weights_tensor(w, {n}), weights_tensor(scores, {n}));
   }, py::arg("D"), py::arg("m"), py::arg("iters") = 16,
      "DnC spectral-filtering weights and outlier scores from squared distances (fp32 [n] each)");
+  m.def("cpu_caf_weights", [](const at::Tensor& D, int f, int iters, int max_passes) {
+    TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_caf_weights: D must be [n, n]");
+    const int64_t n = D.size(0);
+    TORCH_CHECK(f >= 0 && n >= 2 * static_cast<int64_t>(f) + 1 && iters >= 1 && max_passes >= 0,
+                "cpu_caf_weights: 0 <= f, n >= 2f + 1, iters >= 1 and max_passes >= 0 (0 = n)");
+    std::vector<float> lams;
+    auto w = garfield::cpu::caf_weights(dist_from(D), n, f, iters, max_passes, &lams);
+    return py::make_tuple(weights_tensor(w, {n}), weights_tensor(lams, {n}));
+  }, py::arg("D"), py::arg("f"), py::arg("iters") = 16, py::arg("max_passes") = 0,
+     "CAF covariance-filter weights and the top eigenvalue of every pass from squared distances (fp32 [n] each)");
   m.def("cpu_nnm_mix", [](const at::Tensor& D, int f) {
     TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_nnm_mix: D must be [n, n]");
     const int64_t n = D.size(0);

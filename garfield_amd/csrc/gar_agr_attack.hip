@@ -111,7 +111,7 @@ template <int CTRL> __device__ __forceinline__ double agr_dpp_f64(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// Σ over the wave in a fixed pairing, as gar_dnc.hip's wave_sum_dpp: four steps inside a row of 16 lanes
+// Σ over the wave in a fixed pairing, as gar_select.hpp's wave_sum_dpp: four steps inside a row of 16 lanes
 // through DPP, two across rows through the LDS crossbar. One per estimate row and trip of the statistics
 // pass, so the DPP steps matter here.
 __device__ __forceinline__ double agr_wave_sum(double v) {

@@ -242,6 +242,87 @@ std::vector<float> dnc_weights(const std::vector<double>& D, size_t n, size_t m,
   return w;
 }
 
+// CAF covariance filter on the distance matrix alone (docs/GAR_SEMANTICS.md "Covariance filter"): per
+// pass `iters` power rounds on M = A^½ K A^½, K_ij = (x_i - μ_a)·(x_j - μ_a) (never stored), every sum in
+// index order over the valid rows; the weights of the pass of smallest λ are kept.
+std::vector<float> caf_weights(const std::vector<double>& D, size_t n, size_t f, size_t iters, size_t max_passes,
+                               std::vector<float>* lams_out) {
+  const auto [valid, nv] = valid_rows(D, n, n);
+  std::vector<float> lams(n, static_cast<float>(kInf));
+  if (nv == 0) {
+    if (lams_out) *lams_out = lams;
+    return std::vector<float>(n, static_cast<float>(1.0 / static_cast<double>(n)));
+  }
+  const Usable dist{D, n};
+  if (max_passes == 0 || max_passes > n) max_passes = n;
+  const double keep_above = static_cast<double>(n) - 2.0 * static_cast<double>(f);
+  std::vector<double> c(n, 0.0), a(n, 0.0), ra(n, 0.0), s(n, 0.0), p(n, 0.0), b(n, 0.0), u(n, 0.0), kp(n, 0.0),
+      best_a(n, 0.0);
+  for (size_t i = 0; i < n; ++i) c[i] = valid[i] ? 1.0 : 0.0;
+  double q = 0.0;
+  // kp = K p = -½ (D p - s Σp - (s·p) 1 + q Σp 1) on the valid rows
+  auto apply_K = [&]() {
+    double sp = 0.0, sdp = 0.0;
+    for (size_t i = 0; i < n; ++i)
+      if (valid[i]) { sp += p[i]; sdp += s[i] * p[i]; }
+    for (size_t i = 0; i < n; ++i) {
+      if (!valid[i]) continue;
+      double acc = 0.0;
+      for (size_t j = 0; j < n; ++j)
+        if (valid[j]) acc += dist(i, j) * p[j];
+      kp[i] = -0.5 * (acc - s[i] * sp - sdp + q * sp);
+    }
+  };
+  double best = kInf;
+  for (size_t pass = 0;; ++pass) {
+    double sc = 0.0;
+    for (size_t i = 0; i < n; ++i) sc += c[i];
+    if (pass == 0)
+      for (size_t i = 0; i < n; ++i) best_a[i] = c[i] / sc;
+    if (!(sc > keep_above && pass < max_passes)) break;
+    for (size_t i = 0; i < n; ++i) {
+      a[i] = c[i] / sc;
+      ra[i] = std::sqrt(a[i]);
+    }
+    q = 2.0 * dist_quadratic(dist, valid, a, s);
+    size_t star = 0;   // the lowest index that attains max a_i (s_i - q/2)
+    for (size_t i = 1; i < n; ++i)
+      if (a[i] * (s[i] - 0.5 * q) > a[star] * (s[star] - 0.5 * q)) star = i;
+    std::fill(p.begin(), p.end(), 0.0);
+    p[star] = ra[star];
+    apply_K();
+    for (size_t i = 0; i < n; ++i) b[i] = ra[i] * kp[i];
+    for (size_t it = 0; it < iters; ++it) {
+      double nb = 0.0;
+      for (size_t i = 0; i < n; ++i) nb += b[i] * b[i];
+      nb = std::sqrt(nb);
+      for (size_t i = 0; i < n; ++i) {
+        u[i] = nb > 0.0 ? b[i] / nb : 0.0;
+        p[i] = ra[i] * u[i];
+      }
+      apply_K();
+      for (size_t i = 0; i < n; ++i) b[i] = ra[i] * kp[i];
+    }
+    double lam = 0.0;
+    for (size_t i = 0; i < n; ++i) lam += u[i] * b[i];
+    if (lam < best) {   // strict: the first pass wins a tie
+      best = lam;
+      best_a = a;
+    }
+    lams[pass] = static_cast<float>(lam);
+    double tmax = 0.0;   // over the rows that still carry weight
+    for (size_t i = 0; i < n; ++i)
+      if (c[i] > 0.0 && lam > 0.0) tmax = std::max(tmax, kp[i] * kp[i] / lam);
+    if (!(lam > 0.0 && tmax > 0.0)) break;
+    for (size_t i = 0; i < n; ++i)
+      if (c[i] > 0.0) c[i] *= 1.0 - std::min(kp[i] * kp[i] / lam / tmax, 1.0);
+  }
+  std::vector<float> w(n, 0.f);
+  for (size_t i = 0; i < n; ++i) w[i] = static_cast<float>(best_a[i]);
+  if (lams_out) *lams_out = lams;
+  return w;
+}
+
 // Centered clipping on the distance matrix alone (docs/GAR_SEMANTICS.md "Centered clipping"):
 // exactly `iters` rounds, every sum in index order.
 std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t nw, const std::vector<double>& a0,

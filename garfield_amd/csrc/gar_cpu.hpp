@@ -46,6 +46,14 @@ std::vector<float> cclip_weights(const std::vector<double>& D, size_t n, size_t 
 std::vector<float> dnc_weights(const std::vector<double>& D, size_t n, size_t m, size_t iters,
                                std::vector<float>* scores = nullptr);
 
+// CAF covariance filter (from D alone; docs/GAR_SEMANTICS.md): while more than n - 2f rows' worth of weight
+// is left (at most max_passes passes, 0 = n), `iters` power rounds give the top eigenpair of the weighted
+// covariance and every row is down-weighted by its squared projection on it; the weights of the pass of
+// smallest λ are returned. lams[n] = λ of pass p at index p, +inf beyond the last pass; rows without a finite
+// off-diagonal distance get weight 0 and use up the budget; none valid -> uniform 1/n.
+std::vector<float> caf_weights(const std::vector<double>& D, size_t n, size_t f, size_t iters, size_t max_passes,
+                               std::vector<float>* lams = nullptr);
+
 // Nearest-neighbour mixing on D alone (0 <= f < n, c = n - f; docs/GAR_SEMANTICS.md). nnm_mix: masks[2n]
 // (row i's set, i and its c - 1 nearest, as two 64-bit words; n <= 128) and the squared distances D' of
 // the mixed rows (+inf diagonal), for the selections above. nnm_unmix: the selection's weights a over

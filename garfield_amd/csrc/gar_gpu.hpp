@@ -23,7 +23,7 @@ void gram(const RowTable& rows, int n, int64_t d, int dt, float* slabs, int grid
           float* gram, hipStream_t stream);
 
 // ---- Selection (one workgroup, on device, no host round-trip) --------------
-// krum, bulyan, geomed, cclip, dnc, nnm_mix and nnm_sets share gar_select.hpp: the distances from the Gram, the
+// krum, bulyan, geomed, cclip, dnc, caf, nnm_mix and nnm_sets share gar_select.hpp: the distances from the Gram, the
 // validity policy, and launch_select (1024 threads per problem, n <= kMaxRows).
 // weights[n] (fp32), order[n] (gradient ids by increasing score), scores[n]
 // batch > 1: `batch` independent problems, gram [batch][np][np] -> weights/order/scores [batch][n]
@@ -50,6 +50,14 @@ void cclip_select(const float* gram, int np, int n, int nw, const float* a0, dou
 // principal direction (+inf on rows without a finite distance); weights[n] = 1 / kv on the
 // kv = min(m, |V|) valid rows of lowest (score, index), 0 elsewhere. batch as krum_select.
 void dnc_select(const float* gram, int np, int n, int m, int iters, float* weights, float* scores,
+                hipStream_t stream, int batch = 1);
+
+// CAF covariance filter (gar_caf.hip): while more than n - 2f rows' worth of weight is left (at most
+// max_passes passes, 0 = n), `iters` power rounds on M = A^½ K A^½ of the Gram's distances (n <= kMaxRows,
+// K never stored) and a soft down-weighting of every row by its squared projection on the top principal
+// direction of the weighted covariance; weights[n] = the weights of the pass of smallest λ (0 on rows
+// without a finite distance), lams[n] = λ of pass p at index p, +inf beyond the last pass. batch as krum_select.
+void caf_select(const float* gram, int np, int n, int f, int iters, int max_passes, float* weights, float* lams,
                 hipStream_t stream, int batch = 1);
 
 // Nearest-neighbour mixing (gar_nnm.hip), n <= kMaxRows, 0 <= f < n, c = n - f. nnm_mix: from the Gram,

@@ -22,6 +22,28 @@ __device__ __forceinline__ double wave_dot(const double* x, const double* y, int
   return wave_sum_f64(acc);
 }
 
+// v of the lane that the DPP control CTRL pairs with this one (all 64 lanes active)
+template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
+  hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+
+// Σ over the wave, the same bits in every lane, in a fixed pairing (DnC, CAF). A round is a chain of four
+// dependent sums, so their latency is the kernel's time: the four steps inside a row of 16 lanes go
+// through DPP (lane ^ 1, lane ^ 2, then the mirrored half rows and rows: both partners add the same
+// two values) and only the two steps across rows through the LDS crossbar (wave_sum_f64 takes six).
+__device__ __forceinline__ double wave_sum_dpp(double v) {
+  v += dpp_f64<0xB1>(v);    // quad_perm [1, 0, 3, 2]
+  v += dpp_f64<0x4E>(v);    // quad_perm [2, 3, 0, 1]
+  v += dpp_f64<0x141>(v);   // row_half_mirror
+  v += dpp_f64<0x140>(v);   // row_mirror
+  v += __shfl_xor(v, 16, 64);
+  v += __shfl_xor(v, 32, 64);
+  return v;
+}
+
 // Squared distances D (LDS, pitch n + 1) from a Gram matrix (pitch np) by the whole workgroup:
 // non-finite -> +inf, clamped at 0, `diag` on the diagonal.
 __device__ __forceinline__ void fill_distances(const float* __restrict__ gram, int np, int n, float* D,

@@ -163,6 +163,38 @@ static void test_cclip() {
   CHECK(std::fabs(v - (2.575 + 0.25 * (-2.575 - 2.475 - 2.375 + 2.575))) < 1e-5);
 }
 
+// The covariance filter on points on a line (the covariance is a scalar, τ_i = (x_i - μ)²): the first pass
+// zeroes the farther colluder, the second the other one, the third runs on the honest points alone, has the
+// smallest λ and is kept; its update leaves less than n - 2f = 5 rows' worth of weight. The non-finite
+// row takes no weight.
+static void test_caf() {
+  const size_t n = 9, f = 2;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double pos[n] = {0.0, 0.1, 0.2, 0.3, 0.0 /* non-finite */, 0.15, 0.25, 10.0, 10.1};
+  std::vector<double> D(n * n, inf);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < n; ++j)
+      if (i != j && i != 4 && j != 4) D[i * n + j] = (pos[i] - pos[j]) * (pos[i] - pos[j]);
+  std::vector<float> lams;
+  auto w = cpu::caf_weights(D, n, f, 16, 0, &lams);
+  CHECK(w.size() == n && lams.size() == n);
+  CHECK(std::isfinite(lams[0]) && std::isfinite(lams[1]) && std::isfinite(lams[2]) && std::isinf(lams[3]));
+  CHECK(lams[0] > lams[1] && lams[1] > lams[2] && lams[2] > 0.f);
+  CHECK(w[4] == 0.f && w[7] == 0.f && w[8] == 0.f);
+  double tot = 0.0;
+  for (size_t i = 0; i < n; ++i) {
+    CHECK(w[i] >= 0.f);
+    tot += w[i];
+  }
+  CHECK(std::fabs(tot - 1.0) < 1e-6);
+  // one pass at most: uniform on the valid rows; f = 0: no pass at all
+  w = cpu::caf_weights(D, n, f, 16, 1, &lams);
+  for (size_t i = 0; i < n; ++i) CHECK(w[i] == (i == 4 ? 0.f : 0.125f));
+  CHECK(std::isfinite(lams[0]) && std::isinf(lams[1]));
+  w = cpu::caf_weights(D, n, 0, 16, 0, &lams);
+  CHECK(w[0] == 0.125f && w[4] == 0.f && std::isinf(lams[0]));
+}
+
 // Worker momentum on exactly sized buffers (an access outside them is the sanitizer's to find): bf16
 // rows with a row stride, a range inside the row; powers of two make every value exact.
 static void test_worker_momentum() {
@@ -209,6 +241,7 @@ int main() {
   test_gars();
   test_nnm();
   test_cclip();
+  test_caf();
   test_worker_momentum();
   test_mailbox();
   if (failures) {

@@ -32,7 +32,7 @@ tail by LDS radix select; the Krum/Bulyan Gram as a split-K MFMA kernel with fp3
 Bulyan's W·X on fp32 MFMA);
 everything else, and the CPU, uses a vectorised PyTorch implementation.
 
-The distance-based selections (Krum, geometric median, centered clipping, DnC, Brute, Bulyan, and the
+The distance-based selections (Krum, geometric median, centered clipping, DnC, CAF, Brute, Bulyan, and the
 mixing in front of them) are resolved and dispatched in ``ops/selection.py``; :func:`selection_weights`
 picks the backend for a gradient set.
 """
@@ -333,7 +333,9 @@ def selection_weights(gradients, sel: Selection) -> torch.Tensor:
     if cuda:
         D = pairwise_distances(rows.obj)
     else:
-        D = ref.pairwise_sqdist(rows.stacked()) if C is None else C.cpu_pairwise(rows.obj)
+        # the C++ distances take MAX_ROWS rows; beyond them (a rule without a Gram form: caf) the oracle's
+        host = C is None or rows.n > MAX_ROWS
+        D = ref.pairwise_sqdist(rows.stacked()) if host else C.cpu_pairwise(rows.obj)
     if sel.clips:   # distances lose the norms ARC decides from: they travel beside D
         return sel.on_host(C, D, _sqnorms(rows)).to(rows.device)
     return sel.on_host(C, D).to(rows.device)
@@ -394,6 +396,30 @@ def dnc(gradients, f: int = 0, m: int | None = None, iters: int = 16, **_) -> to
     of the rows kept by :func:`dnc_weights`."""
     rows = prepare(gradients)
     return combine(rows, dnc_weights(rows, f, m, iters))
+
+
+# CAF, the covariance filter (docs/GAR_SEMANTICS.md): the top eigenpair of the weighted covariance
+# Σ_i a_i (x_i - μ_a)(x_i - μ_a)ᵀ comes from power rounds on the n x n matrix A^½ K A^½ of the Gram's distances,
+# every row is down-weighted by its squared projection on the top direction, pass after pass, and the
+# weights of the pass of smallest top eigenvalue go to the combine kernels.
+
+
+def caf_weights(gradients, f: int, iters: int = 16, max_passes: int | None = None,
+                pre: str | None = None) -> torch.Tensor:
+    """Weights of the CAF covariance filter ([n] fp32 on the gradients' device): while more than n - 2f rows'
+    worth of weight is left (at most ``max_passes`` passes, None: n), ``iters`` power rounds on the pairwise
+    distances alone and a soft down-weighting along the top principal direction of the weighted covariance; the
+    weights of the pass whose covariance had the smallest top eigenvalue. ``pre="arc"``: the row weights of
+    CAF over the adaptively clipped rows (:func:`arc_weights`)."""
+    rows = prepare(gradients)
+    return selection_weights(rows, resolve("caf", rows.n, f, None, pre, {"iters": iters, "max_passes": max_passes}))
+
+
+def caf(gradients, f: int = 0, iters: int = 16, max_passes: int | None = None, **_) -> torch.Tensor:
+    """CAF, the covariance-bound agnostic filter (Allouah et al.): Σ_i a_i g_i with the weights of
+    :func:`caf_weights`."""
+    rows = prepare(gradients)
+    return combine(rows, caf_weights(rows, f, iters, max_passes))
 
 
 # Centered clipping (CC; docs/GAR_SEMANTICS.md): v <- v + (1/n) Σ_i (x_i - v) min(1, tau / ||x_i - v||). The
@@ -630,8 +656,8 @@ def arc_scales(gradients, f: int) -> torch.Tensor:
 def arc_weights(gradients, f: int, rule: str = "krum", nnm: bool = False, **kw) -> torch.Tensor:
     """Weights over the ORIGINAL rows ([n] fp32 on the gradients' device) of ``rule`` (krum: ``m``; geomed:
     ``iters``, ``nu``; cclip: ``tau``, ``iters``, ``start`` "mean" / "krum", ``m``; dnc: ``m``, ``iters``;
-    average) applied to the adaptively clipped rows; ``nnm``: to those rows mixed over their n - f nearest
-    (not dnc). The weights sum to at most 1: a clipped row counts with its scale."""
+    caf: ``iters``, ``max_passes``; average) applied to the adaptively clipped rows; ``nnm``: to those rows mixed
+    over their n - f nearest (not dnc, caf). The weights sum to at most 1: a clipped row counts with its scale."""
     rows = prepare(gradients)
     return selection_weights(rows, resolve(rule, rows.n, f, kw.pop("m", None), _arc_pre(nnm), kw))
 
@@ -1015,6 +1041,7 @@ RULES = {
     "geomed": geomed,
     "cclip": cclip,
     "dnc": dnc,
+    "caf": caf,
     "nnm-cclip": lambda gradients, f=0, tau=None, iters=3, start="mean", m=None, **_: nnm(
         gradients, f, "cclip", tau=tau, iters=iters, start=start, m=m),
     "nnm-krum": lambda gradients, f, m=None, **_: nnm(gradients, f, "krum", m=m),
@@ -1027,6 +1054,8 @@ RULES = {
     "arc-cclip": lambda gradients, f=0, tau=None, iters=3, start="mean", m=None, **_: arc(
         gradients, f, "cclip", tau=tau, iters=iters, start=start, m=m),
     "arc-dnc": lambda gradients, f=0, m=None, iters=16, **_: arc(gradients, f, "dnc", m=m, iters=iters),
+    "arc-caf": lambda gradients, f=0, iters=16, max_passes=None, **_: arc(gradients, f, "caf", iters=iters,
+                                                                          max_passes=max_passes),
     "arc-average": lambda gradients, f=0, **_: arc(gradients, f, "average"),
     "arc-nnm-krum": lambda gradients, f, m=None, **_: arc(gradients, f, "krum", True, m=m),
     "arc-nnm-geomed": lambda gradients, f=0, iters=32, nu=1e-6, **_: arc(gradients, f, "geomed", True, iters=iters,

@@ -290,6 +290,113 @@ def dnc(G, f: int, m: int | None = None, iters: int = 16) -> torch.Tensor:
     return combine(X, dnc_weights(pairwise_sqdist(X), m, iters)[0].double())
 
 
+# CAF, the covariance filter (docs/GAR_SEMANTICS.md "Covariance filter"): the rows are down-weighted along
+# the top principal direction of their weighted covariance, pass after pass, and the weighted mean whose
+# covariance had the smallest top eigenvalue is kept. With μ_a = Σ a_i x_i and K_ij = (x_i - μ_a)·(x_j - μ_a),
+# the n x n matrix M = A^½ K A^½ has the non-zero eigenvalues of the d x d covariance Σ_i a_i (x_i - μ_a)(x_i - μ_a)ᵀ,
+# and K comes from the squared distances alone: everything below works on D.
+
+
+def _caf_distances(D: torch.Tensor) -> tuple:
+    """(usable distances [n, n] fp64 with zeros on the diagonal, on invalid rows and where infinite; valid [n])."""
+    D = D.detach().to(device="cpu", dtype=torch.float64)
+    fin = torch.isfinite(D)
+    fin.fill_diagonal_(False)
+    return torch.where(fin, D, torch.zeros_like(D)), fin.any(1)
+
+
+def caf_pass(D: torch.Tensor, valid: torch.Tensor, a: torch.Tensor, iters: int = 16) -> tuple:
+    """One pass of the covariance filter on the usable distances ``D`` with the weights ``a`` (fp64, Σ a = 1,
+    zero on invalid rows): ``(λ, τ [n])``, the top eigenvalue of the weighted covariance after exactly ``iters``
+    power rounds on M = A^½ K A^½ from its column at the row of largest a_i ‖x_i - μ_a‖², and the squared
+    projections of the centred rows on the top eigenvector (0 on invalid rows, and everywhere if λ <= 0)."""
+    n = D.shape[0]
+    ra = a.sqrt()
+    s = D @ a
+    q = float(a @ s)
+    zero = torch.zeros(n, dtype=torch.float64)
+
+    def K(p):
+        sp = float(p.sum())
+        return torch.where(valid, -0.5 * (D @ p - s * sp - float(s @ p) + q * sp), zero)
+
+    v = (a * (s - 0.5 * q)).tolist()
+    star = 0   # the lowest index that attains the maximum
+    for i in range(n):
+        if v[i] > v[star]:
+            star = i
+    p = zero.clone()
+    p[star] = ra[star]
+    b = ra * K(p)
+    u, kp = zero, zero
+    for _ in range(iters):
+        nb = math.sqrt(float(b @ b))
+        u = b / nb if nb > 0.0 else zero
+        kp = K(ra * u)
+        b = ra * kp
+    lam = float(u @ b)
+    return lam, (kp * kp / lam if lam > 0.0 else zero)
+
+
+def caf_trace(D: torch.Tensor, f: int, iters: int = 16, max_passes: int | None = None) -> dict:
+    """The covariance filter with its decisions laid open (all fp64): ``weights`` [n] (the a of the pass of
+    smallest λ), ``lams`` (λ per pass), ``sums`` (Σc at every loop test), ``taus`` (per pass, τ on the rows that
+    still carry weight, descending) and ``best`` (the pass kept; None when no pass ran)."""
+    n = D.shape[0]
+    D, valid = _caf_distances(D)
+    out = {"lams": [], "sums": [], "taus": [], "best": None}
+    if not bool(valid.any()):
+        out["weights"] = torch.full((n,), 1.0 / n, dtype=torch.float64)
+        return out
+    c = valid.double()
+    best, best_a = math.inf, c / float(c.sum())
+    limit = n if max_passes is None else max_passes
+    while True:
+        sc = float(c.sum())
+        out["sums"].append(sc)
+        if not (sc > n - 2 * f and len(out["lams"]) < limit):
+            break
+        a = c / sc
+        lam, tau = caf_pass(D, valid, a, iters)
+        if lam < best:   # strict: the first pass wins a tie
+            best, best_a, out["best"] = lam, a, len(out["lams"])
+        out["lams"].append(lam)
+        live = c > 0
+        out["taus"].append(sorted(tau[live].tolist(), reverse=True))
+        tmax = float(tau[live].max())
+        if not (lam > 0.0 and tmax > 0.0):
+            break
+        c = torch.where(live, c * (1.0 - (tau / tmax).clamp(max=1.0)), c)
+    out["weights"] = best_a
+    return out
+
+
+def caf_weights(D: torch.Tensor, f: int, iters: int = 16, max_passes: int | None = None) -> tuple:
+    """(w [n], lams [n]), both fp32: the weights of the covariance filter on the squared distances ``D`` and
+    the λ of pass p at index p, +inf beyond the last pass. No valid row: uniform 1/n."""
+    n = D.shape[0]
+    t = caf_trace(D, f, iters, max_passes)
+    lams = torch.full((n,), math.inf, dtype=torch.float64)
+    lams[:len(t["lams"])] = torch.tensor(t["lams"], dtype=torch.float64)
+    return t["weights"].float(), lams.float()
+
+
+def caf_dense_pass(X, a) -> tuple:
+    """The check on the vectors themselves: (λ, τ [n]) from the d x d weighted covariance
+    Σ_i a_i (x_i - μ_a)(x_i - μ_a)ᵀ, its top eigenvalue and the squared projections of the centred rows on
+    its top eigenvector (``torch.linalg.eigh``)."""
+    X = _g(X)
+    a = torch.as_tensor(a, dtype=torch.float64)
+    C = X - (a[:, None] * X).sum(0, keepdim=True)
+    ev, vec = torch.linalg.eigh(C.T @ (a[:, None] * C))
+    return float(ev[-1]), (C @ vec[:, -1]) ** 2
+
+
+def caf(G, f: int, iters: int = 16, max_passes: int | None = None) -> torch.Tensor:
+    X = _g(G)
+    return combine(X, caf_weights(pairwise_sqdist(X), f, iters, max_passes)[0].double())
+
+
 # Nearest-neighbour mixing (docs/GAR_SEMANTICS.md "Nearest-neighbour mixing"): every gradient is
 # replaced by the mean of its c = n - f nearest gradients, itself included, before a rule runs.
 # Mixing is linear, so everything below works on the squared distances alone.
@@ -459,7 +566,7 @@ def arc_clip(X, f: int) -> torch.Tensor:
 
 
 def arc_weights(X, f: int, rule: str = "krum", nnm: bool = False, **kw) -> torch.Tensor:
-    """Weights [n] (fp64) over the ORIGINAL rows of ``rule`` (krum / geomed / cclip / dnc / average) over the
+    """Weights [n] (fp64) over the ORIGINAL rows of ``rule`` (krum / geomed / cclip / dnc / caf / average) over the
     clipped rows, behind the mixing when ``nnm``: w_j = c_j a_j."""
     X = _g(X)
     n = X.shape[0]
@@ -476,10 +583,12 @@ def arc_weights(X, f: int, rule: str = "krum", nnm: bool = False, **kw) -> torch
         a = cclip_weights(D, n, a0, kw.get("tau"), f, kw.get("iters", 3))
     elif rule == "dnc":
         a = dnc_weights(D, n - f if kw.get("m") is None else kw["m"], kw.get("iters", 16))[0]
+    elif rule == "caf":
+        a = caf_weights(D, f, kw.get("iters", 16), kw.get("max_passes"))[0]
     elif rule == "average":
         a = torch.full((n,), 1.0 / n, dtype=torch.float64)
     else:
-        raise ValueError(f"arc: unsupported rule {rule!r} (krum, geomed, cclip, dnc, average)")
+        raise ValueError(f"arc: unsupported rule {rule!r} (krum, geomed, cclip, dnc, caf, average)")
     return c * a.double()
 
 

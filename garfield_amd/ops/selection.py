@@ -1,6 +1,6 @@
 """The distance-based selections, dispatched from one table.
 
-Krum, the geometric median, centered clipping, DnC, Brute and Bulyan all decide from the pairwise
+Krum, the geometric median, centered clipping, DnC, CAF, Brute and Bulyan all decide from the pairwise
 squared distances of the gradients alone and end in a weight vector over the rows (Bulyan: ``W [t, n]``,
 one row per selection round). "Which selection, with which arguments, on which backend" is decided here
 and nowhere else:
@@ -32,7 +32,7 @@ from garfield_amd.ops import reference as ref
 MAX_ROWS = 128
 CCLIP_STARTS = ("mean", "krum")
 NNM_RULES = ("krum", "geomed", "cclip", "average")
-ARC_RULES = ("krum", "geomed", "cclip", "dnc", "average")
+ARC_RULES = ("krum", "geomed", "cclip", "dnc", "caf", "average")
 # the pre-aggregations: the rules each takes, and its prefix in the registry's names and in messages
 PRE_RULES = {"nnm": NNM_RULES, "arc": ARC_RULES, "arc+nnm": NNM_RULES}
 PRE_TAGS = {"nnm": "nnm", "arc": "arc", "arc+nnm": "arc-nnm"}
@@ -375,6 +375,19 @@ def _dnc_gram(s, g):
     return dnc_weights_from_gram(g, s.m, s.iters)
 
 
+def _caf_device(s, C, g, ws, batch):
+    """The λ of every pass lands in the workspace's ``scores`` buffer."""
+    w = _buf(ws, batch, "weights", s.n)
+    C.gpu_caf_select(g, s.n, s.f, s.iters, s.max_passes, w, _buf(ws, batch, "scores", s.n), batch)
+    return w
+
+
+def _caf_host(s, C, D):
+    if C is None:
+        return ref.caf_weights(D, s.f, s.iters, s.max_passes or None)[0]
+    return C.cpu_caf_weights(D, s.f, s.iters, s.max_passes)[0]
+
+
 def _cclip_device(s, C, g, ws, batch):
     """For ``start="krum"`` k_krum_select writes the start into the weights buffer, then k_cclip_select
     iterates in place. Rows nw..n-1 are basis-only; ``tau <= 0``: from the data."""
@@ -452,6 +465,8 @@ TABLE = {
     "geomed": _Rule(_geomed_device, _geomed_host, _geomed_gram),
     "cclip": _Rule(_cclip_device, _cclip_host, _cclip_gram),
     "dnc": _Rule(_dnc_device, _dnc_host, _dnc_gram),
+    # no vectorised Gram form: the pass count depends on the data, and that form may not sync with the host
+    "caf": _Rule(_caf_device, _caf_host, None),
     "brute": _Rule(_brute_device, _brute_host, None, device_rows=64),
     "bulyan": _Rule(_bulyan_device, _bulyan_host, _bulyan_gram, gram_on_cpu=False),
 }
@@ -477,7 +492,8 @@ class Selection:
     n: int
     f: int
     m: int | None = None       # krum, bulyan: rows kept per round; dnc: rows kept; cclip: of its Krum start
-    iters: int | None = None   # geomed, cclip, dnc
+    iters: int | None = None   # geomed, cclip, dnc; caf: power rounds per pass
+    max_passes: int = 0        # caf: the most passes, as the launchers take it, 0 = n
     nu: float | None = None    # geomed
     tau: float = 0.0           # cclip: the radius as the launchers take it, 0 = from the data
     start: object = "mean"     # cclip: "mean", "krum", "center" (the appended row nw) or an [n] weight tensor
@@ -582,7 +598,7 @@ class Selection:
 def resolve(rule: str, n: int, f: int, m: int | None = None, pre: str | None = None,
             gar_kwargs: dict | None = None) -> Selection:
     """The :class:`Selection` of ``rule`` over ``n`` rows: defaults applied, arguments validated (ValueError).
-    ``gar_kwargs``: the rule's own keyword arguments (``iters``, ``nu``, ``tau``, ``start``); others are ignored."""
+    ``gar_kwargs``: the rule's own keyword arguments (``iters``, ``nu``, ``tau``, ``start``, ``max_passes``); others are ignored."""
     kw = gar_kwargs or {}
     start = kw.get("start")
     start = "mean" if start is None else start
@@ -616,6 +632,15 @@ def resolve(rule: str, n: int, f: int, m: int | None = None, pre: str | None = N
         if not 1 <= m <= n:
             raise ValueError(f"dnc: expected 1 <= m <= n, got m = {m}, n = {n}")
         return Selection(rule, n, f, m=int(m), iters=iters, pre=pre)
+    if rule == "caf":
+        iters, max_passes = kw.get("iters", 16), kw.get("max_passes")
+        if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+            raise ValueError(f"caf: expected an int iters >= 1, got {iters!r}")
+        if max_passes is not None and (isinstance(max_passes, bool) or not isinstance(max_passes, int) or max_passes < 1):
+            raise ValueError(f"caf: expected max_passes None (n) or an int >= 1, got {max_passes!r}")
+        if isinstance(f, bool) or not isinstance(f, int) or f < 0 or n < 2 * f + 1:
+            raise ValueError(f"caf: expected 0 <= f and n >= 2f + 1, got n = {n}, f = {f!r}")
+        return Selection(rule, n, f, iters=iters, max_passes=0 if max_passes is None else min(max_passes, n), pre=pre)
     if rule == "cclip":
         iters, tau = kw.get("iters", 3), kw.get("tau")
         if iters is None or int(iters) < 1:

@@ -107,7 +107,7 @@ class EngineConfig:
     # sharded path with n > 128 rows on the GPU. None: exactly today's paths.
     # "arc": adaptive robust clipping before the rule (the 2f(n - f) // n rows of largest norm scaled down to
     # the next one's norm; docs/GAR_SEMANTICS.md), folded into the Gram and the row weights for gar in
-    # {krum, geomed, cclip, dnc, average}; gar in {trimmed-mean, median} gets the clipped exchange rows
+    # {krum, geomed, cclip, dnc, caf, average}; gar in {trimmed-mean, median} gets the clipped exchange rows
     # rewritten in place, then runs unchanged. "arc+nnm": ARC, then NNM, then the rule, for what "nnm" takes.
     # Same paths and the same refusals as "nnm".
     pre_aggregation: str | None = None

@@ -78,7 +78,7 @@ def layerwise_device_ok(rule: str, n: int, f: int) -> bool:
         return gar.bulyan_sizes(n, f)[0] <= 64
     if rule == "brute":
         return n <= 64
-    return True   # krum, geomed, cclip, dnc (batched one-workgroup selections: n <= MAX_ROWS), aksel
+    return True   # krum, geomed, cclip, dnc, caf (batched one-workgroup selections: n <= MAX_ROWS), aksel
 
 
 def shard_pad(world: int, base: int = 64) -> int:
@@ -667,6 +667,9 @@ class ShardedAggregator:
             mats[b.lo] = self._matrix(b)
         if rule == "brute":   # C(n, f) subsets of n > 128 rows: the device search takes n <= 64
             raise ValueError(f"brute: n must be <= 64 on the GPU (n = {n})")
+        if rule in DISTANCE_RULES and not e._sel.has_gram_form(True):   # caf: its pass count depends on the data
+            raise ValueError(f"{rule}: the sharded aggregation of more than {gar.MAX_ROWS} rows needs a selection "
+                             "vectorised on the Gram (shard_gar=False runs the unsharded path)")
         if rule in DISTANCE_RULES:
             total = None
             for b in self.buckets:

@@ -17,7 +17,8 @@ Reference: ``pytorch_impl/libs/aggregators/__init__.py:15-97``.
   references); ``cclip`` (centered clipping, absent from both references); ``nnm-krum`` /
   ``nnm-geomed`` / ``nnm-cclip`` / ``nnm-average`` (nearest-neighbour mixing before the rule, absent from
   both references); ``dnc`` (DnC spectral filtering, absent from both references); ``caf`` (the CAF
-  covariance filter, absent from both references); ``arc-<rule>`` and
+  covariance filter, absent from both references); ``smea`` (smallest maximum eigenvalue averaging, the
+  exact subset search, absent from both references); ``arc-<rule>`` and
   ``arc-nnm-<rule>`` (adaptive robust clipping before the rule or before the mixing, absent from both references).
 """
 from __future__ import annotations
@@ -60,7 +61,7 @@ def register(name, unchecked, check, upper_bound=None, influence=None):
 
 
 _MODULES = ("average", "median", "krum", "bulyan", "brute", "aksel", "condense", "trimmed_mean",
-            "average_nan", "averaged_median", "geomed", "cclip", "nnm", "dnc", "caf", "arc")
+            "average_nan", "averaged_median", "geomed", "cclip", "nnm", "dnc", "caf", "smea", "arc")
 for _m in _MODULES:
     importlib.import_module(f"garfield_amd.aggregators.{_m}")
 

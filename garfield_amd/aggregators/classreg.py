@@ -179,6 +179,15 @@ class CAFGAR(_GAR):
         return kw
 
 
+class SMEAGAR(_GAR):
+    """SMEA, the subset search scored by the top eigenvalue (new, absent from the reference); ``iters:<int>`` optional."""
+    rule_name = "smea"
+    defaults = {"iters": 16}
+
+    def kwargs(self):
+        return {"iters": int(self.args["iters"])}
+
+
 class NNMKrumGAR(KrumGAR):
     """Multi-Krum after nearest-neighbour mixing over the n - f nearest (new, absent from the reference)."""
     rule_name = "nnm-krum"
@@ -210,5 +219,5 @@ for _name, _cls in (("average", AverageGAR), ("average-nan", AverageNaNGAR), ("m
                     ("condense", CondenseGAR), ("trimmed-mean", TrimmedMeanGAR),
                     ("geomed", GeoMedGAR), ("nnm-krum", NNMKrumGAR), ("nnm-geomed", NNMGeoMedGAR),
                     ("nnm-average", NNMAverageGAR), ("cclip", CClipGAR), ("nnm-cclip", NNMCClipGAR),
-                    ("dnc", DnCGAR), ("caf", CAFGAR)):
+                    ("dnc", DnCGAR), ("caf", CAFGAR), ("smea", SMEAGAR)):
     register(_name, _cls)

@@ -45,7 +45,7 @@ def add_common(p: argparse.ArgumentParser, ps: bool = True) -> argparse.Argument
     p.add_argument("--gar", type=str, default="average",
                    help="GAR name (garfield_amd.aggregators.gars): average, median, krum, bulyan, brute, aksel, condense, "
                         "trimmed-mean, averaged-median, average-nan, geomed, cclip, dnc (DnC spectral filtering), "
-                        "caf (CAF covariance filter), nnm-*, arc-*")
+                        "caf (CAF covariance filter), smea (the exact subset search by top eigenvalue, small n), nnm-*, arc-*")
     p.add_argument("--pre_aggregation", type=str, default=None, choices=["nnm", "arc", "arc+nnm"],
                    help="nnm: nearest-neighbour mixing before --gar (krum, geomed, cclip, average): every gradient is "
                         "replaced by the mean of its n - f nearest, for heterogeneous (--non_iid) data; arc: adaptive "

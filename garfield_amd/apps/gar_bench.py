@@ -24,7 +24,7 @@ from garfield_amd.ops import gar
 
 RULES = ["average", "krum", "bulyan", "median", "trimmed-mean", "averaged-median", "aksel", "brute", "condense",
          "average-nan", "geomed", "nnm-krum", "nnm-geomed", "nnm-average", "cclip", "cclip-krum", "nnm-cclip",
-         "nnm-trimmed-mean", "nnm-median", "dnc", "caf",
+         "nnm-trimmed-mean", "nnm-median", "dnc", "caf", "smea",
          "arc-krum", "arc-geomed", "arc-cclip", "arc-dnc", "arc-caf", "arc-average", "arc-nnm-krum", "arc-nnm-geomed",
          "arc-nnm-cclip", "arc-nnm-average", "arc-trimmed-mean", "arc-median", "arc-nnm-trimmed-mean", "arc-nnm-median"]
 # "cclip-krum": centered clipping from the Multi-Krum start (start="krum"), Krum's f
@@ -117,6 +117,9 @@ def main(argv=None):
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     p.add_argument("--list-input", action="store_true", help="pass a list of n tensors instead of [n, d]")
+    p.add_argument("--f", type=int, default=None,
+                   help="the f of every rule that takes one, instead of the sweep's default (at most 2, 3 for bulyan); "
+                        "also lifts the sweep's n <= 20 limit on the subset searches brute and smea")
     p.add_argument("--worker_momentum", type=float, default=None, metavar="BETA",
                    help="time the worker-momentum pass alone instead of the rules, on --n rows (as k) of --d coordinates")
     a = p.parse_args(argv)
@@ -134,10 +137,12 @@ def main(argv=None):
             inp = [G[i].clone() for i in range(n)] if a.list_input else G
             for rule in a.rules:
                 f = default_f(rule, n)
-                if rule in ("krum", "nnm-krum", "cclip-krum", "bulyan", "brute", "aksel", "trimmed-mean", "condense",
+                if a.f is not None and f is not None:
+                    f = a.f
+                if rule in ("krum", "nnm-krum", "cclip-krum", "bulyan", "brute", "smea", "aksel", "trimmed-mean", "condense",
                             "nnm-trimmed-mean", "nnm-median") + tuple(r for r in RULES if r.startswith("arc-")) and f is None:
                     continue
-                if rule == "brute" and n > 20:
+                if rule in ("brute", "smea") and n > 20 and a.f is None:
                     continue
                 ms = bench_rule(rule, inp, f, a.iters, a.warmup)
                 nbytes = n * d * G.element_size()

@@ -70,7 +70,7 @@ def parse(argv=None):
                         "25,50 for resnet50, as the reference's MultiStepLR, trainer.py:273-274,290-291; none else)")
     p.add_argument("--lr_gamma", type=float, default=0.1)
     p.add_argument("--num_iter", type=int, default=0, help="stop after this many iterations (0: epochs)")
-    p.add_argument("--aggregator", default="vanilla", help="GAR name; vanilla = average (reference default); the new rules geomed, cclip, dnc and caf included")
+    p.add_argument("--aggregator", default="vanilla", help="GAR name; vanilla = average (reference default); the new rules geomed, cclip, dnc, caf and smea included")
     p.add_argument("--pre_aggregation", default=None, choices=["nnm", "arc", "arc+nnm"],
                    help="nnm: nearest-neighbour mixing before --aggregator (krum, geomed, cclip, average); arc: adaptive "
                         "robust clipping before it (also dnc, caf, trimmed-mean, median); arc+nnm: the clipping, then the mixing")

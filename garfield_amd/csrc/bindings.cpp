@@ -2290,6 +2290,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     garfield::gpu::brute_select(fptr(gram), garfield::gpu::gram_padded(n), n, f,
                                 reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>()), fptr(w), stream_of(gram.device()));
   });
+  m.def("gpu_smea_select", [](const at::Tensor& gram, int n, int f, int iters, const at::Tensor& best,
+                              const at::Tensor& w, const at::Tensor& scores) {
+    const int np = check_select("gpu_smea_select", gram, n, 1, {{w, n}, {scores, 1}});
+    TORCH_CHECK(n <= 64 && f >= 0 && f < n && iters >= 1, "gpu_smea_select: n <= 64, 0 <= f < n and iters >= 1");
+    TORCH_CHECK(best.scalar_type() == at::kLong && best.numel() >= 1 && best.device() == gram.device(),
+                "gpu_smea_select: best must be an int64 tensor on the Gram's device");
+    unsigned long long subsets = 1;   // C(n, f): the search keys a subset by its 32-bit rank
+    for (int i = 1, b = std::min(f, n - f); i <= b && !(subsets >> 32); ++i)
+      subsets = subsets * static_cast<unsigned long long>(n - b + i) / static_cast<unsigned long long>(i);
+    TORCH_CHECK(!(subsets >> 32), "gpu_smea_select: more than 2^32 subsets");
+    c10::hip::HIPGuard guard(gram.device().index());
+    garfield::gpu::smea_select(fptr(gram), np, n, f, iters,
+                               reinterpret_cast<unsigned long long*>(best.data_ptr<int64_t>()), fptr(w), fptr(scores),
+                               stream_of(gram.device()));
+  }, py::arg("gram"), py::arg("n"), py::arg("f"), py::arg("iters"), py::arg("best"), py::arg("weights"),
+     py::arg("scores"),
+     "SMEA on device: the subset search scored by power rounds on each subset's block of the Gram's distances; "
+     "weights [n], scores[0] = the winning subset's top eigenvalue");
   m.def("gpu_aksel_select", [](const at::Tensor& slabs, int n, int c, const at::Tensor& w, const at::Tensor& dists) {
     c10::hip::HIPGuard guard(slabs.device().index());
     const int grid = static_cast<int>(slabs.numel() / n);
@@ -2954,6 +2972,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     const int64_t n = D.size(0);
     return weights_tensor(garfield::cpu::brute_weights(dist_from(D), n, f), {n});
   });
+  m.def("cpu_smea_weights", [](const at::Tensor& D, int f, int iters) {
+    TORCH_CHECK(D.dim() == 2 && D.size(0) == D.size(1), "cpu_smea_weights: D must be [n, n]");
+    const int64_t n = D.size(0);
+    TORCH_CHECK(n <= 64 && f >= 0 && f < n && iters >= 1, "cpu_smea_weights: n <= 64, 0 <= f < n and iters >= 1");
+    float lam = 0.f;
+    auto w = garfield::cpu::smea_weights(dist_from(D), n, f, iters, &lam);
+    return py::make_tuple(weights_tensor(w, {n}), weights_tensor(std::vector<float>{lam}, {1}));
+  }, py::arg("D"), py::arg("f"), py::arg("iters") = 16,
+     "SMEA weights (fp32 [n]) and the winning subset's top eigenvalue (fp32 [1]) from squared distances");
   m.def("cpu_aksel_weights", [](const at::Tensor& dists, int c) {
     const int64_t n = dists.numel();
     return weights_tensor(garfield::cpu::aksel_weights(dist_from(dists), n, c), {n});

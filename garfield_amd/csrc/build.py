@@ -35,7 +35,7 @@ HIP_SOURCES = [
     "gar_layerwise.hip", "conv3x3_nhwc.hip", "conv_f32.hip", "sconv_nhwc.hip", "gar_tail_f32.hip",
     "gar_geomed.hip", "gar_nnm.hip", "gar_cclip.hip", "worker_mom.hip",
     "gar_nnm_coord.hip", "gar_nnm_coord_mfma.hip", "gar_dnc.hip", "gar_agr_attack.hip", "gar_arc.hip",
-    "gar_caf.hip",
+    "gar_caf.hip", "gar_smea.hip",
 ]
 TORCH_SOURCES = ["bindings.cpp", "mailbox.cpp", "rccl_direct.cpp"]   # need torch + HIP headers
 PLAIN_SOURCES = ["threadpool.cpp", "gar_cpu.cpp"]  # plain C++17

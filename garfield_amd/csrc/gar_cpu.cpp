@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <limits>
 #include <mutex>
@@ -537,6 +538,101 @@ std::vector<float> brute_weights(const std::vector<double>& D, size_t n, size_t 
   std::vector<float> w(n, 0.f);
   for (size_t i = 0; i < n; ++i)
     if ((mask >> i) & 1ull) w[i] = 1.f / static_cast<float>(k);
+  return w;
+}
+
+// SMEA (docs/GAR_SEMANTICS.md "SMEA"): Brute's enumeration, every subset scored by exactly `iters` power
+// rounds on K_S = -½ J D_S J of its k x k block of the distances (the loop of dnc_weights on the members in
+// increasing index, every sum in index order), λ / k as fp32; the smallest (λ bits, rank) key wins.
+std::vector<float> smea_weights(const std::vector<double>& D, size_t n, size_t f, size_t iters, float* lam_out) {
+  if (n > 64) throw std::invalid_argument("smea: n must be <= 64");
+  const size_t k = n - f;
+  const unsigned long long total = binom(n, k);
+  if (total >> 32) throw std::invalid_argument("smea: more than 2^32 subsets");
+  // clamped at 0, a zero diagonal, +inf where non-finite (a subset with such a pair scores +inf)
+  std::vector<double> Dc(n * n);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < n; ++j) {
+      const double v = D[i * n + j];
+      Dc[i * n + j] = i == j ? 0.0 : (std::isfinite(v) ? std::max(v, 0.0) : kInf);
+    }
+  const double kd = static_cast<double>(k);
+  const size_t nchunks = static_cast<size_t>(std::min<unsigned long long>(total, 256ull));
+  std::vector<unsigned long long> best(nchunks, ~0ull);
+  parallel_for(0, static_cast<size_t>(total), nchunks, [&](size_t c, size_t lo, size_t hi) {
+    unsigned long long mask = unrank_mask(lo, n, k);
+    unsigned long long mine = ~0ull;
+    std::vector<size_t> S(k);
+    std::vector<double> B(k * k), r(k), b(k), u(k), t(k);
+    for (size_t rank = lo; rank < hi; ++rank) {
+      size_t q = 0;
+      for (unsigned long long mi = mask; mi; mi &= mi - 1ull) S[q++] = static_cast<size_t>(__builtin_ctzll(mi));
+      bool finite = true;
+      for (size_t p = 0; p < k; ++p)
+        for (size_t j = 0; j < k; ++j) {
+          B[p * k + j] = Dc[S[p] * n + S[j]];
+          finite = finite && std::isfinite(B[p * k + j]);
+        }
+      float score = static_cast<float>(kInf);
+      if (finite) {
+        for (size_t p = 0; p < k; ++p) {
+          double acc = 0.0;
+          for (size_t j = 0; j < k; ++j) acc += B[p * k + j];
+          r[p] = acc / kd;
+        }
+        double g = 0.0;
+        for (size_t p = 0; p < k; ++p) g += r[p];
+        g /= kd;
+        size_t star = 0;   // the lowest position that attains max κ, κ_p = r_p - g/2
+        for (size_t p = 1; p < k; ++p)
+          if (r[p] - 0.5 * g > r[star] - 0.5 * g) star = p;
+        for (size_t p = 0; p < k; ++p) b[p] = -0.5 * (B[p * k + star] - r[p] - r[star] + g);
+        std::fill(u.begin(), u.end(), 0.0);
+        for (size_t it = 0; it < iters; ++it) {
+          double nu = 0.0;
+          for (size_t p = 0; p < k; ++p) nu += b[p] * b[p];
+          nu = std::sqrt(nu);
+          double cm = 0.0;
+          for (size_t p = 0; p < k; ++p) {
+            u[p] = nu > 0.0 ? b[p] / nu : 0.0;
+            cm += u[p];
+          }
+          cm /= kd;
+          double tm = 0.0;
+          for (size_t p = 0; p < k; ++p) {
+            double acc = 0.0;
+            for (size_t j = 0; j < k; ++j) acc += B[p * k + j] * (u[j] - cm);
+            t[p] = acc;
+            tm += acc;
+          }
+          tm /= kd;
+          for (size_t p = 0; p < k; ++p) b[p] = -0.5 * (t[p] - tm);
+        }
+        double lam = 0.0;
+        for (size_t p = 0; p < k; ++p) lam += u[p] * b[p];
+        score = static_cast<float>(lam / kd);
+        if (!(score >= 0.f)) score = score < 0.f ? 0.f : static_cast<float>(kInf);   // negative: 0; NaN: +inf
+      }
+      uint32_t bits;
+      std::memcpy(&bits, &score, sizeof bits);
+      const unsigned long long key = (static_cast<unsigned long long>(bits) << 32) | rank;
+      if (key < mine) mine = key;
+      const unsigned long long cc = mask & (~mask + 1ull);
+      const unsigned long long rr = mask + cc;
+      mask = (((rr ^ mask) >> 2) / cc) | rr;
+    }
+    best[c] = mine;
+  });
+  unsigned long long key = best[0];   // reduced in a fixed order
+  for (size_t c = 1; c < nchunks; ++c) key = std::min(key, best[c]);
+  const unsigned long long mask = unrank_mask(key & 0xffffffffull, n, k);
+  std::vector<float> w(n, 0.f);
+  for (size_t i = 0; i < n; ++i)
+    if ((mask >> i) & 1ull) w[i] = 1.f / static_cast<float>(k);
+  if (lam_out) {
+    const uint32_t bits = static_cast<uint32_t>(key >> 32);
+    std::memcpy(lam_out, &bits, sizeof bits);
+  }
   return w;
 }
 

@@ -30,6 +30,11 @@ std::vector<float> krum_weights(const std::vector<double>& D, size_t n, size_t f
                                 std::vector<double>* scores = nullptr);
 std::vector<float> bulyan_weights(const std::vector<double>& D, size_t n, size_t f, size_t m, size_t t);
 std::vector<float> brute_weights(const std::vector<double>& D, size_t n, size_t f);
+// SMEA (docs/GAR_SEMANTICS.md): among the C(n, n - f) subsets in Brute's order (n <= 64), 1 / (n - f) on the
+// members of the one whose covariance has the smallest top eigenvalue λ (`iters` power rounds on the subset's
+// block of D, fp32, ties to the lowest rank; +inf with a non-finite pair); *lam = the winning λ.
+std::vector<float> smea_weights(const std::vector<double>& D, size_t n, size_t f, size_t iters,
+                                float* lam = nullptr);
 std::vector<float> aksel_weights(const std::vector<double>& dists, size_t n, size_t c);
 // Geometric median (smoothed Weiszfeld, `iters` rounds on D alone): rows without a finite
 // off-diagonal distance get weight 0; none valid -> uniform 1/n.

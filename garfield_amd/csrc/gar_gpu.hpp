@@ -101,6 +101,13 @@ void bulyan_select(const float* gram, int np, int n, int f, int m, int t, float*
 void brute_select(const float* gram, int np, int n, int f, unsigned long long* best,
                   float* weights, hipStream_t stream);
 
+// SMEA (gar_smea.hip): Brute's subset search with every (n - f)-subset scored by `iters` power rounds on its
+// block of the Gram's distances (the top eigenvalue of the members' covariance), n <= 64 and at most 2^32
+// subsets. best: one uint64 (initialised here), weights[n] = 1 / (n - f) on the winner's members, scores[0] =
+// its eigenvalue. No batched form: one launch per problem.
+void smea_select(const float* gram, int np, int n, int f, int iters, unsigned long long* best, float* weights,
+                 float* scores, hipStream_t stream);
+
 // ---- Weighted combine  out = Σ_j w_j g_j  (optionally fused SGD update) -----
 void combine(const RowTable& rows, int n, int64_t d, int dt, const float* weights,
              void* out, int out_dt, hipStream_t stream);

@@ -295,14 +295,7 @@ __global__ __launch_bounds__(1024) void k_bulyan_select(const float* __restrict_
 
 // Brute: smallest-diameter subset of size k = n - f among C(n, k), enumerated
 // as k-bit masks in increasing numeric order (combinatorial number system).
-__device__ __forceinline__ unsigned long long binom(int a, int b) {
-  if (b < 0 || b > a) return 0ull;
-  if (b > a - b) b = a - b;
-  unsigned long long r = 1;
-  for (int i = 1; i <= b; ++i) r = r * static_cast<unsigned long long>(a - b + i) / static_cast<unsigned long long>(i);
-  return r;
-}
-
+// binom, the unrank and the init / finalize kernels are shared with the SMEA search: gar_select.hpp.
 __global__ __launch_bounds__(256) void k_brute_search(const float* __restrict__ gram, int np, int n, int k,
                                                       unsigned long long total, unsigned long long per,
                                                       unsigned long long* __restrict__ best) {
@@ -319,13 +312,7 @@ __global__ __launch_bounds__(256) void k_brute_search(const float* __restrict__ 
   const unsigned long long tid = static_cast<unsigned long long>(blockIdx.x) * blockDim.x + threadIdx.x;
   const unsigned long long r0 = tid * per;
   if (r0 < total) {
-    // Unrank r0.
-    unsigned long long r = r0, mask = 0ull;
-    int kk = k;
-    for (int i = n - 1; i >= 0 && kk > 0; --i) {
-      const unsigned long long c = binom(i, kk);
-      if (c <= r) { mask |= 1ull << i; r -= c; --kk; }
-    }
+    unsigned long long mask = subset_unrank(r0, n, k);
     unsigned long long r1 = r0 + per;
     if (r1 > total) r1 = total;
     for (unsigned long long rank = r0; rank < r1; ++rank) {
@@ -362,25 +349,6 @@ __global__ __launch_bounds__(256) void k_brute_search(const float* __restrict__ 
     for (int w = 1; w < 4; ++w) b = wbest[w] < b ? wbest[w] : b;
     atomicMin(best, b);
   }
-}
-
-__global__ void k_brute_init(unsigned long long* best) { *best = ~0ull; }
-
-__global__ void k_brute_finalize(const unsigned long long* __restrict__ best, int n, int k,
-                                 float* __restrict__ weights) {
-  __shared__ unsigned long long mask;
-  if (threadIdx.x == 0) {
-    unsigned long long r = (*best) & 0xffffffffull, msk = 0ull;
-    int kk = k;
-    for (int i = n - 1; i >= 0 && kk > 0; --i) {
-      const unsigned long long c = binom(i, kk);
-      if (c <= r) { msk |= 1ull << i; r -= c; --kk; }
-    }
-    mask = msk;
-  }
-  __syncthreads();
-  const int i = threadIdx.x;
-  if (i < n) weights[i] = ((mask >> i) & 1ull) ? 1.f / static_cast<float>(k) : 0.f;
 }
 
 }  // namespace
@@ -477,9 +445,10 @@ void brute_select(const float* gram_in, int np, int n, int f, unsigned long long
   if (per < 1) per = 1;
   const unsigned long long threads = (total + per - 1) / per;
   const unsigned int blocks = static_cast<unsigned int>((threads + 255) / 256);
-  hipLaunchKernelGGL(k_brute_init, dim3(1), dim3(1), 0, stream, best);
+  hipLaunchKernelGGL(k_subset_init<>, dim3(1), dim3(1), 0, stream, best);
   hipLaunchKernelGGL(k_brute_search, dim3(blocks), dim3(256), 0, stream, gram_in, np, n, k, total, per, best);
-  hipLaunchKernelGGL(k_brute_finalize, dim3(1), dim3(64), 0, stream, best, n, k, weights);
+  hipLaunchKernelGGL(k_subset_finalize<false>, dim3(1), dim3(64), 0, stream, best, n, k, weights,
+                     static_cast<float*>(nullptr));
 }
 
 }  // namespace gpu

@@ -1,5 +1,6 @@
 // What the one-workgroup selections on the n x n Gram matrix share (Krum, Bulyan, geometric median,
-// centered clipping, DnC, nearest-neighbour mixing): one 1024-thread workgroup (16 waves) per problem,
+// centered clipping, DnC, nearest-neighbour mixing; at the end, what the subset searches share): one
+// 1024-thread workgroup (16 waves) per problem,
 // the distances D in LDS with pitch n + 1, row i on wave i % 16, each lane owning columns
 // (lane, lane + 64), n <= kMaxRows = 128. The validity policy of docs/GAR_SEMANTICS.md is written
 // here once for the GPU (load_valid_distances, zero_infinite_distances) and once for the CPU
@@ -173,7 +174,47 @@ __device__ __forceinline__ void nnm_build_sets(const float* D, int n, int c, uns
   }
 }
 
+// The subset searches (Brute, SMEA): the k-subsets of n rows as k-bit masks in increasing numeric order
+// (combinatorial number system), rank = the position in that order.
+__device__ __forceinline__ unsigned long long binom(int a, int b) {
+  if (b < 0 || b > a) return 0ull;
+  if (b > a - b) b = a - b;
+  unsigned long long r = 1;
+  for (int i = 1; i <= b; ++i) r = r * static_cast<unsigned long long>(a - b + i) / static_cast<unsigned long long>(i);
+  return r;
+}
+
+// the mask of rank r
+__device__ __forceinline__ unsigned long long subset_unrank(unsigned long long r, int n, int k) {
+  unsigned long long mask = 0ull;
+  int kk = k;
+  for (int i = n - 1; i >= 0 && kk > 0; --i) {
+    const unsigned long long c = binom(i, kk);
+    if (c <= r) { mask |= 1ull << i; r -= c; --kk; }
+  }
+  return mask;
+}
+
 }  // namespace dev
+
+// The searches reduce a (score bits << 32) | rank key with atomicMin: the key's start value, and the winner's
+// weights 1 / k on its members (kScore: also the winning score, the key's high word, to *score).
+// (a kernel defined in a header shared by two translation units: the dummy template parameter gives it the
+// linkage of a template, one definition at link time)
+template <int = 0> __global__ void k_subset_init(unsigned long long* best) { *best = ~0ull; }
+
+template <bool kScore>
+__global__ void k_subset_finalize(const unsigned long long* __restrict__ best, int n, int k,
+                                  float* __restrict__ weights, float* __restrict__ score) {
+  __shared__ unsigned long long mask;
+  if (threadIdx.x == 0) {
+    mask = dev::subset_unrank((*best) & 0xffffffffull, n, k);
+    if (kScore) *score = __uint_as_float(static_cast<unsigned int>((*best) >> 32));
+  }
+  __syncthreads();
+  const int i = threadIdx.x;
+  if (i < n) weights[i] = ((mask >> i) & 1ull) ? 1.f / static_cast<float>(k) : 0.f;
+}
 
 // Launch a selection kernel: `batch` workgroups of 1024 threads with lds_bytes of dynamic LDS. At
 // n = 128 the distances alone are 64.5 KB, above the 64 KB default, so every kernel is opted in to

@@ -195,6 +195,29 @@ static void test_caf() {
   CHECK(w[0] == 0.125f && w[4] == 0.f && std::isinf(lams[0]));
 }
 
+// SMEA on points on a line (the covariance is a scalar: λ of a subset is its members' variance): the five
+// honest points win, the two colluders and the non-finite row take no weight; with f = 0 every subset holds
+// the non-finite row, scores +inf, and rank 0 (all rows) wins; k = 1 scores 0 and rank 0 is row 0.
+static void test_smea() {
+  const size_t n = 8, f = 3;
+  const double inf = std::numeric_limits<double>::infinity();
+  const double pos[n] = {0.0, 0.1, 0.2, 0.3, 0.0 /* non-finite */, 0.15, 10.0, 10.0};
+  std::vector<double> D(n * n, inf);
+  for (size_t i = 0; i < n; ++i)
+    for (size_t j = 0; j < n; ++j)
+      if (i != j && i != 4 && j != 4) D[i * n + j] = (pos[i] - pos[j]) * (pos[i] - pos[j]);
+  float lam = -1.f;
+  auto w = cpu::smea_weights(D, n, f, 16, &lam);
+  CHECK(w.size() == n);
+  for (size_t i = 0; i < n; ++i) CHECK(w[i] == ((i == 4 || i >= 6) ? 0.f : 0.2f));
+  CHECK(std::fabs(lam - 0.01f) < 1e-6f);
+  w = cpu::smea_weights(D, n, 0, 16, &lam);
+  for (size_t i = 0; i < n; ++i) CHECK(w[i] == 0.125f);
+  CHECK(std::isinf(lam));
+  w = cpu::smea_weights(D, n, n - 1, 16, &lam);
+  CHECK(w[0] == 1.f && w[1] == 0.f && lam == 0.f);
+}
+
 // Worker momentum on exactly sized buffers (an access outside them is the sanitizer's to find): bf16
 // rows with a row stride, a range inside the row; powers of two make every value exact.
 static void test_worker_momentum() {
@@ -242,6 +265,7 @@ int main() {
   test_nnm();
   test_cclip();
   test_caf();
+  test_smea();
   test_worker_momentum();
   test_mailbox();
   if (failures) {

@@ -20,7 +20,7 @@ _RULES = {"Average": "average", "Median": "median", "Krum": "krum", "Brute": "br
           "Condense": "condense", "Bulyan": "bulyan", "TrimmedMean": "trimmed-mean",
           "AverageNan": "average-nan", "AveragedMedian": "averaged-median",
           "GeoMed": "geomed", "NNM-Krum": "nnm-krum", "NNM-GeoMed": "nnm-geomed", "NNM-Average": "nnm-average",
-          "CClip": "cclip", "NNM-CClip": "nnm-cclip", "DnC": "dnc", "CAF": "caf"}
+          "CClip": "cclip", "NNM-CClip": "nnm-cclip", "DnC": "dnc", "CAF": "caf", "SMEA": "smea"}
 
 
 class Aggregator_tf:

@@ -32,7 +32,7 @@ tail by LDS radix select; the Krum/Bulyan Gram as a split-K MFMA kernel with fp3
 Bulyan's W·X on fp32 MFMA);
 everything else, and the CPU, uses a vectorised PyTorch implementation.
 
-The distance-based selections (Krum, geometric median, centered clipping, DnC, CAF, Brute, Bulyan, and the
+The distance-based selections (Krum, geometric median, centered clipping, DnC, CAF, Brute, SMEA, Bulyan, and the
 mixing in front of them) are resolved and dispatched in ``ops/selection.py``; :func:`selection_weights`
 picks the backend for a gradient set.
 """
@@ -48,6 +48,7 @@ from garfield_amd import _native
 from garfield_amd.ops import reference as ref
 # the distance-based selections live in ops/selection.py; their Gram forms keep their names here
 from garfield_amd.ops.selection import (ARC_RULES, BRUTE_MAX_SUBSETS, CCLIP_STARTS, MAX_ROWS, NNM_RULES,  # noqa: F401
+                                        SMEA_MAX_SUBSETS,
                                         Selection, arc_count, arc_distances, arc_gram, arc_scales_from_sqnorms,
                                         cclip_weights_from_gram, distances_from_gram,
                                         dnc_weights_from_gram, geomed_weights_from_gram, krum_weights_from_gram,
@@ -912,6 +913,26 @@ def brute(gradients, f: int, **_) -> torch.Tensor:
     return combine(rows, brute_weights(rows, f))
 
 
+# SMEA, smallest maximum eigenvalue averaging (docs/GAR_SEMANTICS.md): Brute's subset search with every
+# (n - f)-subset scored by the top eigenvalue of its members' covariance, which power rounds on the subset's
+# block of the Gram's distances give without touching the d-length rows.
+
+
+def smea_weights(gradients, f: int, iters: int = 16, pre: str | None = None) -> torch.Tensor:
+    """Weights of SMEA ([n] fp32 on the gradients' device): 1 / (n - f) on the members of the (n - f)-subset
+    whose empirical covariance has the smallest top eigenvalue (``iters`` power rounds per subset on the
+    pairwise distances alone, ties to the lowest rank in Brute's order), 0 elsewhere. ``pre`` is refused:
+    no pre-aggregation runs in front of SMEA yet."""
+    rows = prepare(gradients)
+    return selection_weights(rows, resolve("smea", rows.n, f, None, pre, {"iters": iters}))
+
+
+def smea(gradients, f: int = 0, iters: int = 16, **_) -> torch.Tensor:
+    """SMEA (Allouah et al., ICML 2023): the mean of the subset chosen by :func:`smea_weights`."""
+    rows = prepare(gradients)
+    return combine(rows, smea_weights(rows, f, iters))
+
+
 def aksel_count(n: int, f: int, mode: str = "mid") -> int:
     """The rows Aksel keeps: the closer half (``mode`` "mid"), else all but f."""
     return (n + 1) // 2 if mode == "mid" else n - f
@@ -1042,6 +1063,7 @@ RULES = {
     "cclip": cclip,
     "dnc": dnc,
     "caf": caf,
+    "smea": smea,
     "nnm-cclip": lambda gradients, f=0, tau=None, iters=3, start="mean", m=None, **_: nnm(
         gradients, f, "cclip", tau=tau, iters=iters, start=start, m=m),
     "nnm-krum": lambda gradients, f, m=None, **_: nnm(gradients, f, "krum", m=m),

@@ -197,20 +197,13 @@ def cclip(G, f: int = 0, tau: float | None = None, iters: int = 3, start="mean",
     return combine(X, cclip_weights(D, n, a0, tau, f, iters))
 
 
-def dnc_scores(D: torch.Tensor, iters: int = 16) -> torch.Tensor:
-    """Outlier scores [n] (fp64, before the cast to fp32) of the DnC spectral filter on the squared distances
-    alone (docs/GAR_SEMANTICS.md "Spectral filtering"). With the rows centred at their mean, C Cᵀ = K = -½ J D J,
-    and the score of row i, its squared projection on the top right singular vector of C, is λ u_i² for the
-    top eigenpair (λ, u) of K. Exactly ``iters`` power rounds from the column of K at the row farthest from
-    the mean, sums in index order. +inf on rows without a finite off-diagonal distance; 0 if there is none."""
-    D = D.detach().to(device="cpu", dtype=torch.float64)
-    n = D.shape[0]
-    fin = [[i != j and math.isfinite(float(D[i, j])) for j in range(n)] for i in range(n)]
-    V = [i for i in range(n) if any(fin[i])]
-    if not V:
-        return torch.zeros(n, dtype=torch.float64)
+def _dnc_power(dist, V, iters: int) -> tuple:
+    """(λ, b): exactly ``iters`` power rounds on K = -½ J D J over the rows ``V`` (indices into the usable
+    distances ``dist``, a list of rows with zeros where unusable), from the column of K at the row farthest from
+    the mean, sums in index order; λ = u·b after the last round, b = K u on ``V`` (0 elsewhere). The loop of
+    :func:`dnc_scores`, shared with :func:`smea_lambda`."""
+    n = len(dist)
     nv = len(V)
-    dist = [[float(D[i, j]) if fin[i][j] else 0.0 for j in range(n)] for i in range(n)]
     r = [0.0] * n
     for i in V:
         acc = 0.0
@@ -253,6 +246,23 @@ def dnc_scores(D: torch.Tensor, iters: int = 16) -> torch.Tensor:
     lam = 0.0
     for i in V:
         lam += u[i] * b[i]
+    return lam, b
+
+
+def dnc_scores(D: torch.Tensor, iters: int = 16) -> torch.Tensor:
+    """Outlier scores [n] (fp64, before the cast to fp32) of the DnC spectral filter on the squared distances
+    alone (docs/GAR_SEMANTICS.md "Spectral filtering"). With the rows centred at their mean, C Cᵀ = K = -½ J D J,
+    and the score of row i, its squared projection on the top right singular vector of C, is λ u_i² for the
+    top eigenpair (λ, u) of K. Exactly ``iters`` power rounds from the column of K at the row farthest from
+    the mean, sums in index order. +inf on rows without a finite off-diagonal distance; 0 if there is none."""
+    D = D.detach().to(device="cpu", dtype=torch.float64)
+    n = D.shape[0]
+    fin = [[i != j and math.isfinite(float(D[i, j])) for j in range(n)] for i in range(n)]
+    V = [i for i in range(n) if any(fin[i])]
+    if not V:
+        return torch.zeros(n, dtype=torch.float64)
+    dist = [[float(D[i, j]) if fin[i][j] else 0.0 for j in range(n)] for i in range(n)]
+    lam, b = _dnc_power(dist, V, iters)
     s = torch.full((n,), math.inf, dtype=torch.float64)
     for i in V:
         s[i] = b[i] * b[i] / lam if lam > 0.0 else 0.0
@@ -728,6 +738,113 @@ def brute_weights(D: torch.Tensor, f: int) -> torch.Tensor:
 
 def brute(G, f: int) -> torch.Tensor:
     return combine(G, brute_weights(pairwise_sqdist(G), f))
+
+
+# SMEA, smallest maximum eigenvalue averaging (docs/GAR_SEMANTICS.md "SMEA"): Brute's enumeration of the
+# (n - f)-subsets, each scored by the top eigenvalue of its members' empirical covariance instead of its
+# diameter. The eigenvalue comes from the power rounds of the DnC filter on the subset's block of the squared
+# distances, so everything below works on D alone.
+
+
+def _smea_distances(D: torch.Tensor) -> torch.Tensor:
+    """Squared distances [n, n] (fp64, CPU) as the selections build them: clamped at 0, a zero diagonal and
+    +inf where non-finite (kept, not zeroed: a subset with such a pair is invalid)."""
+    D = D.detach().to(device="cpu", dtype=torch.float64)
+    D = torch.where(torch.isfinite(D), D.clamp(min=0), torch.full_like(D, math.inf))
+    D.fill_diagonal_(0.0)
+    return D
+
+
+def smea_subsets(n: int, k: int) -> torch.Tensor:
+    """The C(n, k) subsets as ascending member indices [C(n, k), k] (int64), row ``rank`` = the subset whose
+    k-bit mask is the rank-th smallest: Brute's enumeration order."""
+    lex = torch.tensor(list(combinations(range(n), k)), dtype=torch.int64).reshape(-1, k)
+    # numeric order of the masks compares the largest member first: the reverse of the lexicographic
+    # order of the mirrored tuples
+    return (n - 1 - lex).flip(1).flip(0).contiguous()
+
+
+def smea_lambda(D: torch.Tensor, members, iters: int = 16) -> float:
+    """λ of one subset (fp64): the top eigenvalue of the members' empirical covariance (1/k) Σ (x_i - μ)(x_i - μ)ᵀ
+    after exactly ``iters`` power rounds on K_S = -½ J D_S J, members in increasing index, sums in index
+    order (the loop of :func:`dnc_scores` on the sub-matrix, λ / k). +inf if any pair of members has a
+    non-finite distance; 0 for a single member."""
+    D = _smea_distances(D)
+    S = sorted(int(i) for i in members)
+    k = len(S)
+    dist = [[float(D[a, b]) for b in S] for a in S]
+    if any(not math.isfinite(v) for row in dist for v in row):
+        return math.inf
+    if k == 1:
+        return 0.0
+    return _dnc_power(dist, list(range(k)), iters)[0] / k
+
+
+def smea_lambdas(D: torch.Tensor, f: int, iters: int = 16, chunk: int | None = None) -> torch.Tensor:
+    """λ of every (n - f)-subset [C(n, n - f)] (fp64) in rank order: :func:`smea_lambda` vectorised over the
+    subsets (gathered [B, k, k] blocks, batched power rounds, ``chunk`` subsets at a time: None, 32 MB blocks)."""
+    D = _smea_distances(D)
+    n = D.shape[0]
+    k = n - f
+    chunk = max(64, (1 << 22) // (k * k)) if chunk is None else chunk
+    subsets = smea_subsets(n, k)
+    out = torch.empty(subsets.shape[0], dtype=torch.float64)
+    ids = torch.arange(k)
+    for lo in range(0, subsets.shape[0], chunk):
+        S = subsets[lo:lo + chunk]
+        B = torch.arange(S.shape[0])
+        Ds = D[S[:, :, None], S[:, None, :]]
+        bad = ~torch.isfinite(Ds).all(2).all(1)
+        Ds = torch.where(bad[:, None, None], torch.zeros_like(Ds), Ds)
+        if k == 1:
+            out[lo:lo + chunk] = torch.where(bad, math.inf, 0.0)
+            continue
+        r = Ds.sum(2) / k
+        g = r.sum(1, keepdim=True) / k
+        kappa = r - 0.5 * g
+        star = torch.where(kappa == kappa.max(1, keepdim=True).values, ids[None, :], k).min(1).values
+        b = -0.5 * (Ds[B, :, star] - r - r[B, star][:, None] + g)
+        u = torch.zeros_like(b)
+        for _ in range(iters):
+            nu = (b * b).sum(1, keepdim=True).sqrt()
+            u = torch.where(nu > 0, b / nu, torch.zeros_like(b))
+            c = u.sum(1, keepdim=True) / k
+            t = (Ds * (u - c)[:, None, :]).sum(2)
+            b = -0.5 * (t - t.sum(1, keepdim=True) / k)
+        lam = (u * b).sum(1) / k
+        out[lo:lo + chunk] = torch.where(bad, torch.full_like(lam, math.inf), lam)
+    return out
+
+
+def smea_key(lams: torch.Tensor) -> torch.Tensor:
+    """The fp32 score the winner is chosen by: λ cast to fp32, negative values 0 (NaN: +inf)."""
+    s = lams.float().clamp(min=0)
+    return torch.where(torch.isnan(s), torch.full_like(s, math.inf), s)
+
+
+def smea_weights(D: torch.Tensor, f: int, iters: int = 16) -> tuple:
+    """(w [n] fp32, λ fp32 scalar tensor): 1 / (n - f) on the members of the subset of smallest
+    (fp32 λ, rank), 0 elsewhere, and that λ."""
+    n = D.shape[0]
+    k = n - f
+    s = smea_key(smea_lambdas(D, f, iters))
+    rank = int(torch.where(s == s.min(), torch.arange(s.numel()), s.numel()).min())
+    w = torch.zeros(n, dtype=torch.float64)
+    w[smea_subsets(n, k)[rank]] = 1.0 / k
+    return w.float(), s[rank]
+
+
+def smea_dense_lambda(X, members) -> float:
+    """The check on the vectors themselves: the top eigenvalue (``torch.linalg.eigvalsh``) of the members'
+    d x d empirical covariance (1/k) Σ (x_i - μ)(x_i - μ)ᵀ."""
+    X = _g(X)[sorted(int(i) for i in members)]
+    C = X - X.mean(dim=0, keepdim=True)
+    return float(torch.linalg.eigvalsh(C.T @ C / X.shape[0])[-1])
+
+
+def smea(G, f: int, iters: int = 16) -> torch.Tensor:
+    X = _g(G)
+    return combine(X, smea_weights(pairwise_sqdist(X), f, iters)[0].double())
 
 
 def worker_momentum(X, M, beta: float, first: bool, lo: int = 0, hi: int | None = None):

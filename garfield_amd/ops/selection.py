@@ -1,6 +1,6 @@
 """The distance-based selections, dispatched from one table.
 
-Krum, the geometric median, centered clipping, DnC, CAF, Brute and Bulyan all decide from the pairwise
+Krum, the geometric median, centered clipping, DnC, CAF, Brute, SMEA and Bulyan all decide from the pairwise
 squared distances of the gradients alone and end in a weight vector over the rows (Bulyan: ``W [t, n]``,
 one row per selection round). "Which selection, with which arguments, on which backend" is decided here
 and nowhere else:
@@ -37,6 +37,11 @@ ARC_RULES = ("krum", "geomed", "cclip", "dnc", "caf", "average")
 PRE_RULES = {"nnm": NNM_RULES, "arc": ARC_RULES, "arc+nnm": NNM_RULES}
 PRE_TAGS = {"nnm": "nnm", "arc": "arc", "arc+nnm": "arc-nnm"}
 BRUTE_MAX_SUBSETS = 2 ** 32
+# SMEA scores a subset by iters * k^2 multiply-adds where Brute takes k^2 / 2 compares: the most subsets one
+# k_smea_search launch may enumerate. Measured on one MI355X (profiles/r20/smea/): the worst case it admits at
+# n = 32, (n, f) = (32, 8) with 10 518 300 subsets of k = 24, takes 39.0 ms per launch with 16 rounds (3.7 ns per
+# subset; per_n/kernel_stats_n32.csv), far below the one second a launch may hold a shared device: the cap stays at 2^24.
+SMEA_MAX_SUBSETS = 2 ** 24
 
 
 # --------------------------------------------------------------------------- #
@@ -442,6 +447,25 @@ def _brute_host(s, C, D):
     return C.cpu_brute_weights(D, s.f)
 
 
+def _smea_device(s, C, g, ws, batch):
+    """As Brute, the subset search has no batched launcher: one launch per segment. The winning λ lands in
+    slot 0 of the workspace's ``scores`` buffer (per segment: slot 0 of its row)."""
+    w = _buf(ws, batch, "weights", s.n)
+    lam = _buf(ws, batch, "scores", s.n)
+    best = ws.get("smea_best", 1, torch.int64)
+    np2 = C.gram_padded(s.n) ** 2
+    for i in range(batch):
+        C.gpu_smea_select(g[i * np2:(i + 1) * np2], s.n, s.f, s.iters, best, w.view(batch, s.n)[i],
+                          lam.view(batch, s.n)[i])
+    return w
+
+
+def _smea_host(s, C, D):
+    if C is None or s.n > 64:
+        return ref.smea_weights(D, s.f, s.iters)[0]
+    return C.cpu_smea_weights(D, s.f, s.iters)[0]
+
+
 def _bulyan_device(s, C, g, ws, batch):
     W = _buf(ws, batch, "bulyan_W", s.t * s.n)
     C.gpu_bulyan_select(g, s.n, s.f, s.m, s.t, W, batch)
@@ -468,6 +492,8 @@ TABLE = {
     # no vectorised Gram form: the pass count depends on the data, and that form may not sync with the host
     "caf": _Rule(_caf_device, _caf_host, None),
     "brute": _Rule(_brute_device, _brute_host, None, device_rows=64),
+    # the mask is one word, as Brute's; no vectorised Gram form (C(n, f) blocks of k x k)
+    "smea": _Rule(_smea_device, _smea_host, None, device_rows=64),
     "bulyan": _Rule(_bulyan_device, _bulyan_host, _bulyan_gram, gram_on_cpu=False),
 }
 
@@ -492,7 +518,7 @@ class Selection:
     n: int
     f: int
     m: int | None = None       # krum, bulyan: rows kept per round; dnc: rows kept; cclip: of its Krum start
-    iters: int | None = None   # geomed, cclip, dnc; caf: power rounds per pass
+    iters: int | None = None   # geomed, cclip, dnc; caf: power rounds per pass; smea: per subset
     max_passes: int = 0        # caf: the most passes, as the launchers take it, 0 = n
     nu: float | None = None    # geomed
     tau: float = 0.0           # cclip: the radius as the launchers take it, 0 = from the data
@@ -661,6 +687,17 @@ def resolve(rule: str, n: int, f: int, m: int | None = None, pre: str | None = N
             raise ValueError(f"cclip: start must be one of {CCLIP_STARTS} or an [n] weight tensor (n = {n})")
         return Selection(rule, n, f, m=m, iters=int(iters), tau=0.0 if tau is None else float(tau), start=start,
                          nw=n, pre=pre)
+    if rule == "smea":
+        iters = kw.get("iters", 16)
+        if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+            raise ValueError(f"smea: expected an int iters >= 1, got {iters!r}")
+        if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < n:
+            raise ValueError(f"smea: expected 0 <= f < n, got n = {n}, f = {f!r}")
+        subsets = math.comb(n, n - f)
+        if subsets > SMEA_MAX_SUBSETS:
+            raise ValueError(f"smea: C({n}, {n - f}) = {subsets} subsets exceeds {SMEA_MAX_SUBSETS} (2^"
+                             f"{SMEA_MAX_SUBSETS.bit_length() - 1}); use a smaller f or a spectral filter (caf, dnc)")
+        return Selection(rule, n, f, iters=iters, pre=pre)
     if rule == "brute":
         # the device search keys each subset by its 32-bit rank (gar_gram.hip k_brute_*): refuse
         # what it cannot index (C(64, 56) is 4.4e9 subsets: infeasible on any device anyway)

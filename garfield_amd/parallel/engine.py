@@ -597,13 +597,13 @@ class RobustDataParallel:
         one contiguous segment of the memory-order flat layout), then one update.
 
         On the GPU the table's selections run over all segments at once (``_layerwise_device``: a
-        segmented Gram, one batched selection, a segmented combine or Bulyan tail); Brute has no batched
+        segmented Gram, one batched selection, a segmented combine or Bulyan tail); Brute and SMEA have no batched
         launcher and the segmented Bulyan tail takes up to 64 rows. Otherwise a loop over the segments:
         weighted rules compute each segment's weights and combine it in fp32 (exactly the arithmetic of
         the device path), other rules aggregate the segment with the rule itself."""
         gkw = self._rule_kwargs()
         cuda = self.device.type == "cuda"
-        if (cuda and LW_DEVICE and self._sel is not None and rule != "brute"
+        if (cuda and LW_DEVICE and self._sel is not None and rule not in ("brute", "smea")
                 and self.n <= (64 if rule == "bulyan" else gar.MAX_ROWS)):
             self._layerwise_device(first)
             return

@@ -70,13 +70,13 @@ SUPPORTED = DISTANCE_RULES | {"average", "aksel", "median", "trimmed-mean", "ave
 def layerwise_device_ok(rule: str, n: int, f: int) -> bool:
     """Whether the sharded GPU layer-wise path's device kernels take this configuration:
     the segmented Gram (``gpu_lw_gram``) and the batched selections need n <= MAX_ROWS, the
-    layer-wise Bulyan tail t = n - 2f - 2 <= 64 selected rows, Brute's subset search n <= 64.
+    layer-wise Bulyan tail t = n - 2f - 2 <= 64 selected rows, Brute's and SMEA's subset search n <= 64.
     Other configurations keep the unsharded engine's per-segment loop."""
     if n > gar.MAX_ROWS:
         return False
     if rule == "bulyan":
         return gar.bulyan_sizes(n, f)[0] <= 64
-    if rule == "brute":
+    if rule in ("brute", "smea"):
         return n <= 64
     return True   # krum, geomed, cclip, dnc, caf (batched one-workgroup selections: n <= MAX_ROWS), aksel
 
